@@ -19,7 +19,11 @@ Workload: the reference's lattice+cube scene S (example
 with brick_dim 4 (1024 is not a valid size for brick_dim 8, src/boxtree/mod.rs:188-202; the 1024^3 .vox model is not
 in the reference checkout), glass camera of benches/performance.rs on radius 2S at 40 rad aimed at the centre.
 
-Also printed: roofline (algorithmic bytes per launch, counted by the instrumented kernel, / measured kernel time vs
+A plain run sets up, warms up, times the steps, writes the last step's outputs if --dump-outputs DIR is given, and prints
+the line. Everything else sits behind --full: the frame check against a lone trace and the golden digests, the isolated
+launches, the `lone` / `orbit` / `scaling_n1` extras, the multi-GPU per-rank figures and frame check, and the two below.
+
+With --full also printed: roofline (algorithmic bytes per launch, counted by the instrumented kernel, / measured kernel time vs
 8 TB/s; `traffic` = the memory-side read bytes of the same launch, measured in this run by a `rocprofv3 --pmc
 FETCH_SIZE` child run of the same workload (N = 1; --no-pmc, or a failed child run, falls back to the committed
 profiles/traffic.json figure), and cpu_baseline: the CPU restatement of the reference raytracer (oracle/) on the host
@@ -57,6 +61,15 @@ def parse():
                         "environment) as one JSON line and exit, starting nothing")
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--warmup", type=int, default=10)
+    p.add_argument("--full", action="store_true",
+                   help="also run everything besides the headline figure (each still has its own --no-* switch): the "
+                        "frame check, the isolated launches, the `lone` / `orbit` / `scaling_n1` extras, the roofline "
+                        "with its rocprofv3 child run, the CPU baseline and, on the vhx_mgpu path, the per-rank figures "
+                        "and the multi-GPU frame check. Without it a run sets up, warms up, times the steps and prints "
+                        "the line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step left in its caller's buffers as "
+                        "DIR/<name>.npy (dump_outputs)")
     p.add_argument("--size", type=int, default=1024)
     p.add_argument("--brick-dim", type=int, default=4)
     p.add_argument("--width", type=int, default=None, help="frame width (default: by --scaling)")
@@ -221,6 +234,19 @@ def parse_pmc_dir(d, blocks_per_frame=None):
             "lanes": lanes}
 
 
+def child_argv():
+    """This run's arguments for a child run of the same workload: a plain run (no --full) that dumps nothing."""
+    out, skip = [], False
+    for a in sys.argv[1:]:
+        if skip:
+            skip = False
+        elif a == "--dump-outputs":
+            skip = True
+        elif a != "--full" and not a.startswith("--dump-outputs="):
+            out.append(a)
+    return out
+
+
 def measure_traffic(busy_only=False, tune=None, blocks_per_frame=None):
     """Memory-side read bytes per frame, measured now: this bench (same arguments, 5 timed + 1 warm-up frames, no
     roofline / CPU leg) under `rocprofv3 --pmc FETCH_SIZE --kernel-trace` as a child process, FETCH_SIZE summed over
@@ -238,7 +264,7 @@ def measure_traffic(busy_only=False, tune=None, blocks_per_frame=None):
     d = tempfile.mkdtemp(prefix="vhx_pmc_", dir="/tmp")
     counters = ["FETCH_SIZE", "SQ_INSTS_VALU", "SQ_THREAD_CYCLES_VALU", "SQ_ACTIVE_INST_VALU"]
     cmd = ([rp, "--pmc"] + counters + ["--kernel-trace", "-f", "csv", "-d", d, "-o", "pmc", "--", sys.executable,
-                                       os.path.abspath(__file__)] + sys.argv[1:] +
+                                       os.path.abspath(__file__)] + child_argv() +
            ["--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--no-roofline", "--no-pmc",
             "--no-frame-check", "--no-extra", "--no-isolated"] +
            (["--tune", (tune + ";" if tune else "") + "adaptive=0"] if busy_only else []))
@@ -374,6 +400,41 @@ def check_frames(args, rt, rts, outs, last_cam, light, W, H, dev):
     return res
 
 
+DUMP_BUDGET = 63 * 1000 * 1000  # bytes of array data one --dump-outputs may write (under 64 MB with the file headers)
+
+
+def dump_outputs(directory, planes):
+    """--dump-outputs DIR: the planes the last timed step wrote for its caller (name -> host array, one entry or row
+    per pixel of the frame) as DIR/<name>.npy. `rgba` (one packed RGBA8 word per pixel) becomes float32 [n, 4], the
+    word's bytes in memory order; other integer planes (hit values, shadow flags) become float64, exact for 32 bits;
+    float planes stay float32. Every written value is finite: where a float plane holds +inf (the depth of a miss),
+    -inf or NaN, its entry is written as 0 and `<name>_nonfinite.npy` (float32) holds 1, 2 or 3 there and 0 elsewhere;
+    a plane without such entries gets no such file. When the planes together exceed DUMP_BUDGET, every plane holds the same sample of
+    pixels: numpy's default_rng(0) choice without replacement, in ascending pixel order, as many as fit. The scene,
+    the cameras and the sample depend on the arguments only, so two runs with the same arguments write comparable
+    files."""
+    os.makedirs(directory, exist_ok=True)
+    conv = {}
+    for name, a in planes.items():
+        if name == "rgba":
+            conv[name] = (lambda s, a=a: a.view(np.uint8).reshape(-1, 4)[s].astype(np.float32))
+        elif a.dtype.kind in "iu":
+            conv[name] = (lambda s, a=a: a[s].astype(np.float64))
+        else:
+            code = np.where(np.isnan(a), 3, np.where(np.isposinf(a), 1, np.where(np.isneginf(a), 2, 0))).astype(np.uint8)
+            if code.any():  # e.g. the depth of a miss, +inf
+                conv[name] = (lambda s, a=a, code=code: np.where(code[s] == 0, a[s], 0).astype(np.float32))
+                conv[name + "_nonfinite"] = (lambda s, code=code: code[s].astype(np.float32))
+            else:
+                conv[name] = (lambda s, a=a: a[s].astype(np.float32, copy=False))
+    n_pix = len(next(iter(planes.values())))
+    per_pixel = sum(c(slice(0, 1)).nbytes for c in conv.values())
+    n = min(n_pix, DUMP_BUDGET // per_pixel)
+    sel = slice(None) if n == n_pix else np.sort(np.random.default_rng(0).choice(n_pix, size=n, replace=False))
+    for name, c in conv.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(c(sel)))
+
+
 def visible_gpus():
     """GPUs a rank process would see, counted in a child process (torch.cuda.device_count reads the device list
     without initialising HIP; the child keeps even that out of the launcher). -1 if the count failed."""
@@ -477,7 +538,7 @@ def scaling_n1(args):
     VHX_BENCH_MGPU1, frames in flight, the tiles untiled into rank 0's framebuffer) as a child process of this bench
     (its own hardware queues, like every rank of an N > 1 run), 20 timed frames after 5 warm-up frames. Returns the
     sub-object for the line; value(N) / (N x this value) is then like-for-like strong scaling."""
-    cmd = [sys.executable, os.path.abspath(__file__), "--scaling", "strong", "--steps", "20", "--warmup", "5",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--scaling", "strong", "--steps", "20", "--warmup", "5",
            "--size", str(args.size), "--brick-dim", str(args.brick_dim), "--scene", str(args.scene),
            "--tile", str(args.tile), "--planes", str(args.planes), "--no-cpu-baseline", "--no-roofline", "--no-pmc",
            "--no-extra", "--no-isolated"]
@@ -527,6 +588,10 @@ def main():
     args = parse()
     if args.tune in ("", "-"):
         args.tune = None  # "-": the library defaults (scripts that loop over specs)
+    if not args.full:
+        # a plain run does only what the headline figure needs; the multi-GPU extras are gated on args.full below
+        args.no_cpu_baseline = args.no_roofline = args.no_pmc = True
+        args.no_frame_check = args.no_isolated = args.no_extra = True
     if "WORLD_SIZE" not in os.environ:
         if args.gpus is not None and args.gpus > 1:
             sys.exit(launch_ranks(args))
@@ -770,6 +835,7 @@ def main():
     ev = []
     frame = [0]
     last_cam = {}  # context -> camera of its last frame (the frame check after the timed region)
+    last_slot = [0]  # where the last frame went: index into outs (vhx_mgpu: into rank 0's framebuffers)
     NOEV = os.environ.get("VHX_BENCH_NOEV") == "1"
 
     def step(timed):
@@ -778,6 +844,7 @@ def main():
         frame[0] += 1
         r, s_, o = rts[f], streams[f], outs[f]
         last_cam[f] = cam_k
+        last_slot[0] = f if mg is None else 0
         if timed and mg is None and not NOEV:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(s_)
@@ -805,6 +872,7 @@ def main():
         r, s_ = rts[f], streams[f]
         cams_b = [cams[(frame[0] + j) % len(cams)] for j in range(nf)]
         frame[0] += nf
+        last_slot[0] = nf - 1 if mg is not None else f * K + nf - 1
         if mg is not None:
             mg.render_batch(cams_b, None if fbs_rgba is None else fbs_rgba[:nf],
                             None if fbs_depth is None else fbs_depth[:nf])
@@ -901,6 +969,17 @@ def main():
             tt = tt.to(dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        # before any untimed frame below reuses the buffers: the last timed frame as its caller holds it
+        if mg is not None:
+            src = {"rgba": fbs_rgba[last_slot[0]]}
+            if fbs_depth is not None:
+                src["depth"] = fbs_depth[last_slot[0]]
+        elif world > 1:
+            src = {"rgba": framebuffer}
+        else:
+            src = outs[last_slot[0]]
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in src.items()})
     # ---- frame check (untimed, N = 1): the last frame of every context in flight equals one context tracing the
     # same camera alone, and the committed golden digests where the workload is a golden case
     # the schedule the timed frames ran (adaptive by default: the frames-in-flight one once other contexts' frames are
@@ -938,7 +1017,7 @@ def main():
                 iso.append(rt.sync())
         iso_wall.append(time.perf_counter() - tw0)
     kernel_ms_isolated = float(np.median(iso)) if iso else None
-    sched_iso = None if mg is not None else rt.pass_budgets()
+    sched_iso = None if mg is not None or not iso else rt.pass_budgets()
     # ---- extras of an N = 1 line (untimed region): the lone frame -- the reference's call shape,
     # one dispatch per frame (VhxRenderNode::run, src/raytracing/bevy/pipeline/mod.rs:96-155) -- and distinct cameras
     # in flight (an orbiting view, every frame a different camera)
@@ -1016,7 +1095,7 @@ def main():
 
     # ---- multi-GPU per-rank figures (untimed, after the timed region): every rank's trace and transfer device time
     # at the split that was timed, frames one at a time (vhx_mgpu_measure), to test DESIGN.md §7's model ---------------
-    if mg is not None:
+    if mg is not None and args.full:
         tr_ms, tx_ms = mg.measure(cam, frames=4)
         per_rank = [None] * world
         dist.all_gather_object(per_rank, {"rank": rank, "trace_ms": round(tr_ms, 4), "transfer_ms": round(tx_ms, 4),
@@ -1030,7 +1109,7 @@ def main():
 
     # ---- multi-GPU check (untimed): the gathered, untiled frame equals rank 0 tracing the whole frame alone -------
     mgpu = None
-    if world > 1 or mg is not None:
+    if args.full and (world > 1 or mg is not None):
         whole = None
         if rank == 0:
             whole = rt.trace_primary(cam, fields=("rgba", "depth") if mg is not None else ("rgba",))

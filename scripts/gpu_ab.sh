@@ -17,7 +17,7 @@ for rep in $(seq 1 ${REPS:-2}); do
     spec=${S[$k]}
     e=""
     if [ "$spec" = "-" ]; then a=""; elif [ "${spec:0:1}" = "+" ]; then a="${spec:1}"; elif [ "${spec:0:1}" = "=" ]; then a=""; e="${spec:1}"; else a="--tune $spec"; fi
-    env $e timeout -k 10 300 python3 bench.py --steps ${STEPS:-100} --warmup 10 --no-cpu-baseline --no-extra --no-pmc $BENCH_ARGS $a > $D/b${k}_$rep.log 2>&1 || { echo "bench $spec failed"; tail -5 $D/b${k}_$rep.log; exit 1; }
+    env $e timeout -k 10 300 python3 bench.py --full --steps ${STEPS:-100} --warmup 10 --no-cpu-baseline --no-extra --no-pmc $BENCH_ARGS $a > $D/b${k}_$rep.log 2>&1 || { echo "bench $spec failed"; tail -5 $D/b${k}_$rep.log; exit 1; }
     python3 - "$D/b${k}_$rep.log" "$spec" <<'PY'
 import json, sys
 ln = [l for l in open(sys.argv[1]) if l.startswith("{")][-1]

@@ -8,7 +8,7 @@ IFS='|' read -ra S <<< "${TREES:-.}"
 for rep in $(seq 1 ${REPS:-2}); do
   for k in "${!S[@]}"; do
     tr=${S[$k]}
-    (cd "$GRAFT_REPO_ROOT/$tr" && timeout -k 10 300 python3 bench.py --steps ${STEPS:-100} --warmup 10 --no-cpu-baseline --no-extra --no-pmc $BENCH_ARGS) > $D/t${k}_$rep.log 2>&1 || { echo "bench in $tr failed"; tail -5 $D/t${k}_$rep.log; exit 1; }
+    (cd "$tr" && timeout -k 10 300 python3 bench.py --full --steps ${STEPS:-100} --warmup 10 --no-cpu-baseline --no-extra --no-pmc $BENCH_ARGS) > $D/t${k}_$rep.log 2>&1 || { echo "bench in $tr failed"; tail -5 $D/t${k}_$rep.log; exit 1; }
     python3 - "$D/t${k}_$rep.log" "$tr" <<'PY'
 import json, sys
 ln = [l for l in open(sys.argv[1]) if l.startswith("{")][-1]

@@ -10,7 +10,7 @@ if [ -z "$NOTEST" ]; then
   timeout -k 10 600 $T tests/test_gpu_batch.py -m gpu > gpurun_out/${TAG}_pytest.log 2>&1 || { echo "batch tests failed"; tail -40 gpurun_out/${TAG}_pytest.log; exit 1; }
   tail -2 gpurun_out/${TAG}_pytest.log
 fi
-B="python bench.py --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --no-pmc --no-extra"
+B="python bench.py --full --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --no-pmc --no-extra"
 # CFGS: bench configurations separated by '|'
 IFS='|' read -r -a cfgs <<< "${CFGS:---inflight 20|--batch 20 --inflight 1|--batch 20 --inflight 2|--batch 10 --inflight 2}"
 for cfg in "${cfgs[@]}"; do

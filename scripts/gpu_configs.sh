@@ -4,6 +4,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out/configs
 run() {
   local tag="$1"; shift
+  set -- --full "$@"  # the CPU baseline and the roofline printed below are --full figures
   timeout -k 10 300 python bench.py --steps 20 --warmup 3 "$@" > "gpurun_out/configs/$tag.log" 2>&1; local rc=$?
   echo "$tag rc=$rc $(tail -1 "gpurun_out/configs/$tag.log" | python -c "import json,sys; d=json.loads(sys.stdin.read()); c=d.get('cpu_baseline') or {}; r=d.get('roofline') or {}; print(d['value'], 'Mrays/s', d['ms_per_step'], 'ms', 'cpu', c.get('value'), 'frac', r.get('frac'))")"
   return $rc

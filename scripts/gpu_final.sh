@@ -9,6 +9,6 @@ tail -1 $D/smoke.log
 timeout -k 10 900 python -u -m pytest -x -v --timeout 300 --timeout-method thread tests -m gpu > $D/pytest_gpu.log 2>&1 || { echo "gpu suite failed"; tail -30 $D/pytest_gpu.log; exit 1; }
 tail -1 $D/pytest_gpu.log
 cd /tmp && export TMPDIR=/tmp
-timeout -s KILL 240 rocprofv3 --kernel-trace --stats -f csv -d "$D/prof_miplod1" -o ks -- python3 "$R/bench.py" --mip-lod 1 --steps 50 --warmup 5 > "$D/prof_miplod1.log" 2>&1 || { echo "miplod trace failed"; tail -5 "$D/prof_miplod1.log"; exit 1; }
+timeout -s KILL 240 rocprofv3 --kernel-trace --stats -f csv -d "$D/prof_miplod1" -o ks -- python3 "$R/bench.py" --full --mip-lod 1 --steps 50 --warmup 5 > "$D/prof_miplod1.log" 2>&1 || { echo "miplod trace failed"; tail -5 "$D/prof_miplod1.log"; exit 1; }
 tail -1 "$D/prof_miplod1.log" | cut -c1-200
 find "$D" -name "*stats*.csv"

@@ -9,7 +9,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 TAG=$1; shift
 R="$GRAFT_REPO_ROOT"; D="$R/gpurun_out/prof_$TAG"; mkdir -p "$D"
 cd /tmp && export TMPDIR=/tmp
-B="--steps 20 --warmup 5 --no-cpu-baseline"
+B="--full --steps 20 --warmup 5 --no-cpu-baseline"
 timeout -s KILL 180 rocprofv3 --kernel-trace --stats -f csv -d "$D" -o ks -- python3 "$R/bench.py" $B --no-pmc "$@" > "$D/ks.log" 2>&1 || { echo "kernel trace failed"; tail -5 "$D/ks.log"; exit 1; }
 tail -1 "$D/ks.log" | cut -c1-300
 P0="FETCH_SIZE"

@@ -9,7 +9,7 @@ for rep in $(seq 1 ${REPS:-2}); do
   for L in A B; do
     P=$A; [ $L = B ] && P=$B
     E=""; [ "$P" != default ] && E="VHX_LIB=$P"
-    env $E timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra "$@" > $D/${L}_$rep.log 2>&1 \
+    env $E timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extra "$@" > $D/${L}_$rep.log 2>&1 \
       || { tail -20 $D/${L}_$rep.log; exit 1; }
     echo "$L rep $rep $(tail -1 $D/${L}_$rep.log | python3 -c "$J")" | tee -a $D/summary.txt
   done

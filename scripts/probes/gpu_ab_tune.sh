@@ -10,7 +10,7 @@ for rep in $(seq 1 ${REPS:-2}); do
   for S in "$@"; do
     k=$((k+1))
     T=""; [ "$S" != default ] && T="--tune $S"
-    timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra $T $EXTRA > $D/s${k}_$rep.log 2>&1 \
+    timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extra $T $EXTRA > $D/s${k}_$rep.log 2>&1 \
       || { tail -20 $D/s${k}_$rep.log; exit 1; }
     echo "[$S] rep $rep $(tail -1 $D/s${k}_$rep.log | python3 -c "$J")" | tee -a $D/summary.txt
   done

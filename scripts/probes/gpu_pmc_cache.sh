@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 R="$GRAFT_REPO_ROOT"; D="$R/gpurun_out/pmc_cache"; mkdir -p "$D"
 cd /tmp && export TMPDIR=/tmp
-timeout -s KILL 120 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum --kernel-trace -f csv -d "$D" -o c -- python3 "$R/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-roofline > "$D/c.log" 2>&1; rc=$?
+timeout -s KILL 120 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum --kernel-trace -f csv -d "$D" -o c -- python3 "$R/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline --no-roofline > "$D/c.log" 2>&1; rc=$?
 echo "pmc rc=$rc"; [ $rc -ne 0 ] && { tail -5 "$D/c.log"; exit $rc; }
 cd "$R" && python3 - "$D/c_counter_collection.csv" <<'PY'
 import csv, collections, sys

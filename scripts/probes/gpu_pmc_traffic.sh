@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 i=0
 for P in FETCH_SIZE TCC_EA0_RDREQ_sum; do
   i=$((i+1))
-  timeout -k 10 300 rocprofv3 --pmc $P --kernel-trace -f csv -d "$D" -o p$i -- python3 "$R/bench.py" --steps 5 --warmup 1 --no-cpu-baseline --no-roofline > "$D/p$i.log" 2>&1; rc=$?
+  timeout -k 10 300 rocprofv3 --pmc $P --kernel-trace -f csv -d "$D" -o p$i -- python3 "$R/bench.py" --full --steps 5 --warmup 1 --no-cpu-baseline --no-roofline > "$D/p$i.log" 2>&1; rc=$?
   echo "pmc pass $i ($P) rc=$rc"
   [ $rc -ne 0 ] && exit $rc
 done

@@ -9,7 +9,7 @@ for item in $SCHEDULES; do
   i=$((i+1))
   envs="$(echo "$item" | tr '+' ' ')"
   for e in $envs; do export "$e"; done
-  timeout -k 10 120 rocprofv3 --kernel-trace -f csv -d "$D" -o "s$i" -- python3 "$R/bench.py" --steps 4 --warmup 1 --no-cpu-baseline --no-roofline > "$D/s$i.log" 2>&1; rc=$?
+  timeout -k 10 120 rocprofv3 --kernel-trace -f csv -d "$D" -o "s$i" -- python3 "$R/bench.py" --full --steps 4 --warmup 1 --no-cpu-baseline --no-roofline > "$D/s$i.log" 2>&1; rc=$?
   for e in $envs; do unset "${e%%=*}"; done
   echo "[$item] rc=$rc"
   [ $rc -ne 0 ] && exit $rc

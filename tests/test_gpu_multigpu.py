@@ -174,7 +174,7 @@ def test_bench_mgpu_path_one_rank():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, VHX_BENCH_MGPU1="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29541")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--size", "64", "--width", "512", "--height", "256",
-           "--steps", "3", "--warmup", "1", "--inflight", "2", "--no-cpu-baseline", "--no-pmc", "--no-extra"]
+           "--steps", "3", "--warmup", "1", "--inflight", "2", "--full", "--no-cpu-baseline", "--no-pmc", "--no-extra"]
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-4000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])

@@ -2,7 +2,7 @@
 
 Pinning: parse_rotation_matrix against the reference's KATs (magicavoxel.rs:377-404); the rest against an
 independent Python restatement of magicavoxel.rs (below) over .vox files written by this test, and the reference's
-own models when the checkout is present. The .vox reader itself is restated from the file format; dot_vox 5.1.1 is
+own models (stored under tests/golden/, tests/_models.py). The .vox reader itself is restated from the file format; dot_vox 5.1.1 is
 not vendored, so byte-level parity with it is unpinned.
 """
 import ctypes
@@ -15,8 +15,7 @@ import pytest
 import voxelhex_amd as vhx
 from voxelhex_amd import _native as N
 
-REF_MODELS = ["/root/reference/assets/models/navigate.vox",
-              "/root/reference/whisp/assets/models/gingerbread_house_by_kirra_luan.vox"]
+from tests._models import MODELS as REF_MODELS, model_bytes, unpack_model
 
 
 # ----------------------------------------------------------------------------------------------- .vox writer
@@ -392,10 +391,9 @@ def _read_vox(path):
 
 
 @pytest.mark.parametrize("path", REF_MODELS, ids=lambda p: os.path.basename(p))
-def test_reference_models(path):
-    """The reference's own .vox assets (CPU-only; skipped where the checkout is absent)."""
-    if not os.path.exists(path):
-        pytest.skip("reference checkout not present")
+def test_reference_models(path, tmp_path):
+    """The reference's own .vox assets (CPU-only), from the copies stored under tests/golden/."""
+    path = unpack_model(path, tmp_path)
     models, palette, scene = _read_vox(path)
     size, want = py_load(models, palette, scene, 8)
     t = vhx.BoxTree.load_vox_file(path, 8)
@@ -408,18 +406,16 @@ def test_reference_models(path):
         assert e.kind == "Visual" and e.albedo().packed() == want[p], (p, e)
 
 
-def test_gingerbread_fixture_is_the_imported_asset():
-    """tests/golden/gingerbread_bd8.npz (the GPU tests' copy of the reference's gingerbread model) equals what
-    vhx_boxtree_load_vox builds from the asset, where the reference checkout exists."""
+def test_gingerbread_fixture_is_the_imported_asset(tmp_path):
+    """tests/golden/gingerbread_bd8.npz (the GPU tests' flattened tree of the reference's gingerbread model) equals
+    what vhx_boxtree_load_vox builds from the asset (its stored copy under tests/golden/)."""
     import hashlib
     import os
     from tests._arraytree import ArrayTree, FIELDS
     from tests.golden.make_vox_fixture import SRC, build
     fx = ArrayTree(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gingerbread_bd8.npz"))
     assert fx.brick_dim == 8 and fx.boxtree_size == 2048 and fx.desc.node_count > 0
-    if not os.path.exists(SRC):
-        pytest.skip("reference checkout not present (the GPU box): fixture checked for shape only")
-    assert hashlib.sha256(open(SRC, "rb").read()).hexdigest() == fx.source_sha256
-    arrays = build()
+    assert hashlib.sha256(model_bytes(SRC)).hexdigest() == fx.source_sha256
+    arrays = build(unpack_model(SRC, tmp_path))
     for k in FIELDS:
         assert np.array_equal(arrays[k], fx.arrays[k]), k
