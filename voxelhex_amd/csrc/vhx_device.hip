@@ -913,9 +913,8 @@ __global__ void __launch_bounds__(256) k_trace_primary(DevTree t, CamD cam, OutD
 // output index f * npix + j * T * T + y * T + x inside the tile.
 struct TileB {
     uint32_t T, tiles_x, ntiles, stride, bpx, bpt;
-    const uint32_t *starts;
 };
-// VHX_BATCH_WAVES (a variant build): waves per SIMD the batch pass 0 must allow (0: the compiler's choice, 72 VGPRs
+// VHX_BATCH_WAVES (a variant build): waves per SIMD the batch pass 0 must allow (0: the compiler's choice, 70 VGPRs
 // for brick_dim 4 = 7 waves)
 #ifndef VHX_BATCH_WAVES
 #define VHX_BATCH_WAVES 0
@@ -925,44 +924,121 @@ struct TileB {
 #else
 #define VHX_BATCH_ATTR
 #endif
+// Division of a workgroup-uniform index by a launch constant d as a multiply and a shift (Granlund & Montgomery,
+// "Division by invariant integers using multiplication", theorem 4.2 with N = 31): m = ceil(2^(31 + l) / d),
+// l = ceil(log2 d), fits 32 bits and floor(n * m / 2^(31 + l)) = n / d for every n < 2^31 -- block, tile and frame
+// indices all are (trace_batch refuses larger batches). Three scalar instructions instead of a division sequence.
+struct UDiv {
+    uint32_t m, sh;  // d = 0 (a path the launch does not take): m = 0, every quotient 0
+};
+static UDiv udiv_of(uint32_t d) {
+    if (d == 0u) return UDiv{0u, 0u};
+    uint32_t l = 0;
+    while ((1ull << l) < d) ++l;
+    return UDiv{(uint32_t)(((1ull << (31u + l)) + d - 1u) / d), 31u + l};
+}
+__device__ __forceinline__ uint32_t udiv(uint32_t n, const UDiv &d) { return (uint32_t)(((uint64_t)n * d.m) >> d.sh); }
+
+// What the batch pass 0 derives from its launch parameters, computed once on the host (batch_grid): the kernel reads
+// no grid size and divides nothing.
+struct BatchGrid {
+    uint32_t nfr;     // frames in the batch
+    uint32_t xfull;   // xcd_block: the workgroups below this are permuted (0: dispatch order)
+    uint32_t xshift;  // ... log2 of the run length when it is a power of two (shifts), else ~0u (xg)
+    UDiv xg;          // by the run length
+    UDiv split;       // workgroup -> (frame, frame block): by nfr (interleaved) or by nblocks_frame (frame-major)
+    UDiv ltx, bx;     // frame block -> block coordinates: by lo.tx (list order) or by blocks_x (row-major)
+    UDiv bpt, bpx, tiles_x;  // tile sets: by TileB's bpt, bpx and tiles_x
+};
+static BatchGrid batch_grid(uint32_t nblocks, uint32_t nfr, uint32_t nblocks_frame, uint32_t blocks_x, const PassQ &q,
+                            const ListOrder &lo, const TileB &tb) {
+    BatchGrid g{};
+    const uint32_t G = q.xcd_group;
+    g.nfr = nfr;
+    // 8 * G in 64 bits: a run length of 2^29 and more leaves every workgroup in the tail (xcd_block)
+    g.xfull = G && 8ull * G <= nblocks ? (uint32_t)(nblocks / (8ull * G) * (8ull * G)) : 0u;
+    g.xshift = ~0u;
+    if (G && (G & (G - 1u)) == 0u)
+        for (g.xshift = 0; (1u << g.xshift) < G;) ++g.xshift;
+    g.xg = udiv_of(G);
+    g.split = udiv_of(q.finter ? nfr : nblocks_frame);
+    g.ltx = udiv_of(lo.tx);
+    g.bx = udiv_of(blocks_x);
+    g.bpt = udiv_of(tb.bpt);
+    g.bpx = udiv_of(tb.bpx);
+    g.tiles_x = udiv_of(tb.tiles_x);
+    return g;
+}
+// xcd_block and list_block on a workgroup-uniform index with the host's constants: scalar code throughout
+__device__ __forceinline__ uint32_t xcd_block(uint32_t bid, uint32_t G, const BatchGrid &g) {
+    if (bid >= g.xfull) return bid;
+    const uint32_t x = bid & 7u, k = bid >> 3;
+    if (g.xshift != ~0u) return ((((k >> g.xshift) << 3) + x) << g.xshift) + (k & (G - 1u));
+    const uint32_t kq = udiv(k, g.xg);
+    return (kq * 8u + x) * G + (k - kq * G);
+}
+__device__ __forceinline__ void list_block(const ListOrder &lo, const UDiv &ltx, uint32_t b, uint32_t &bx,
+                                           uint32_t &by) {
+    const uint32_t tb = b >> (2u * lo.tbl), m = b & ((1u << (2u * lo.tbl)) - 1u);
+    const uint32_t ty = udiv(tb, ltx);
+    bx = ((tb - ty * lo.tx) << lo.tbl) + compact_bits(m);
+    by = (ty << lo.tbl) + compact_bits(m >> 1);
+}
+
+// The workgroup's position, frame and frame block are the same in every lane by construction; readfirstlane says so
+// to the compiler, which then keeps them, everything derived from them (the block's coordinates, the tile, the
+// addresses of cams[f], outs[f] and starts[f]) and the frame's camera and output pointers in scalar registers: scalar
+// arithmetic, scalar loads, and scalar branches on the null output pointers in store(). Left to itself it computed
+// all of that per lane (about 125 of the 150 vector instructions ahead of the sky test) and read cams[f] and outs[f]
+// with per-lane loads, outs[f] field by field between the stores at the end of every wave. The fixed cost of a wave
+// on the headline path (brick_dim 4, list order, interleaved frames), straight-line instructions: kernel entry to the
+// sky test 307 (169 vector ALU, 11 vector loads) -> 176 (33, 1); sky test to the end of a wave that holds sky only
+// 209 (107 vector ALU, 14 vector memory, 15 waits) -> 185 (83, 6, 4). Pass 0 of the bench frame: 167.2 M -> 146.6 M
+// wave64 VALU instructions, 77 -> 70 VGPRs (6 -> 7 waves per SIMD); profiles/r07/uniform/, DESIGN.md §3.
+// The nine output pointers are read after the traversal, so they hold no scalar registers across it.
 template <int BD, bool FUSE = false>
 __global__ void __launch_bounds__(256) VHX_BATCH_ATTR k_trace_primary_batch(DevTree t, const CamD *__restrict__ cams,
                                                              const OutD *__restrict__ outs, uint32_t nblocks_frame,
-                                                             uint32_t blocks_x, uint32_t npix, PassQ q,
-                                                             ListOrder lo = ListOrder{}, TileB tb = TileB{}) {
+                                                             uint32_t blocks_x, uint32_t npix, PassQ q, BatchGrid bg,
+                                                             ListOrder lo = ListOrder{}, TileB tb = TileB{},
+                                                             const uint32_t *__restrict__ starts = nullptr) {
     __shared__ uint64_t occ_tab[OCC_TAB_WORDS];
     fill_occ_tab(occ_tab);
     zero_ctl(q.zero);
     __syncthreads();
-    const uint32_t bid = xcd_block(blockIdx.x, gridDim.x, q.xcd_group);
+    const uint32_t bid = __builtin_amdgcn_readfirstlane(xcd_block(blockIdx.x, q.xcd_group, bg));
     // frame-major (all of frame 0's blocks, then frame 1's, ...) or interleaved (block sb of every frame in turn: the
     // frames' rays through one screen region run together and share the caches)
-    const uint32_t nfr = gridDim.x / nblocks_frame;
-    const uint32_t f = q.finter ? bid % nfr : bid / nblocks_frame;
-    const uint32_t sb = q.finter ? bid / nfr : bid - f * nblocks_frame;
+    const uint32_t bq = udiv(bid, bg.split);
+    const uint32_t f = __builtin_amdgcn_readfirstlane(q.finter ? bid - bq * bg.nfr : bq);
+    const uint32_t sb = __builtin_amdgcn_readfirstlane(q.finter ? bq : bid - bq * nblocks_frame);
     const CamD cam = cams[f];
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
     uint32_t px, py, local;
     bool valid, entry;  // entry: the position has an output entry (its flag is written)
     if (tb.T) {
-        const uint32_t j = sb / tb.bpt, sbb = sb - j * tb.bpt;
-        const uint32_t lx = (sbb % tb.bpx) * 16u + (wave & 1u) * 8u + (lane & 7u);
-        const uint32_t ly = (sbb / tb.bpx) * 16u + (wave >> 1) * 8u + (lane >> 3);
-        const uint32_t tile = tb.starts[f] + j * tb.stride;
-        px = (tile % tb.tiles_x) * tb.T + lx;
-        py = (tile / tb.tiles_x) * tb.T + ly;
+        const uint32_t j = __builtin_amdgcn_readfirstlane(udiv(sb, bg.bpt)), sbb = sb - j * tb.bpt;
+        const uint32_t sby = udiv(sbb, bg.bpx);
+        const uint32_t lx = (sbb - sby * tb.bpx) * 16u + (wave & 1u) * 8u + (lane & 7u);
+        const uint32_t ly = sby * 16u + (wave >> 1) * 8u + (lane >> 3);
+        // a tile past 2^31 (starts or stride out of range) gets a wrong quotient below and is not valid anyway
+        const uint32_t tile = __builtin_amdgcn_readfirstlane(starts[f] + j * tb.stride);
+        const uint32_t tyy = udiv(tile, bg.tiles_x);
+        px = (tile - tyy * tb.tiles_x) * tb.T + lx;
+        py = tyy * tb.T + ly;
         entry = lx < tb.T && ly < tb.T;
         valid = entry && tile < tb.ntiles && px < cam.width && py < cam.height;
         local = (j * tb.T + ly) * tb.T + lx;
     } else {
         if (lo.tx) {  // this frame's blocks in list order (k_trace_primary)
             uint32_t bx, by;
-            list_block(lo, sb, bx, by);
+            list_block(lo, bg.ltx, sb, bx, by);
             px = bx * 16u + (wave & 1u) * 8u + compact_bits(lane);
             py = by * 16u + (wave >> 1) * 8u + compact_bits(lane >> 1);
         } else {
-            px = (sb % blocks_x) * 16u + (wave & 1u) * 8u + (lane & 7u);
-            py = (sb / blocks_x) * 16u + (wave >> 1) * 8u + (lane >> 3);
+            const uint32_t sby = udiv(sb, bg.bx);
+            px = (sb - sby * blocks_x) * 16u + (wave & 1u) * 8u + (lane & 7u);
+            py = sby * 16u + (wave >> 1) * 8u + (lane >> 3);
         }
         valid = entry = px < cam.width && py < cam.height;
         local = py * cam.width + px;
@@ -985,8 +1061,9 @@ __global__ void __launch_bounds__(256) VHX_BATCH_ATTR k_trace_primary_batch(DevT
                                          nullptr, 0, q.qmode != 0);
         }
         if (done) {
-            store(t, outs[f], local, o, h);
-            if (FUSE && !fused_shadow<BD>(t, occ_tab, q, outs[f], local, h, (uint32_t)idx)) {
+            const OutD out = outs[f];  // one scalar load of the nine pointers
+            store(t, out, local, o, h);
+            if (FUSE && !fused_shadow<BD>(t, occ_tab, q, out, local, h, (uint32_t)idx)) {
                 done = false;
                 tag = VHX_QSHADOW;
             }
@@ -2935,7 +3012,7 @@ static int trace_batch(vhx_ctx *c, const vhx_camera *cams, uint32_t n, const vhx
     src.tiles_x = tiles_x;
     src.tile_stride = stride;
     src.starts = dstarts;
-    const TileB tb{T, tiles_x, ntiles, stride, bpx, bpt, dstarts};
+    const TileB tb{T, tiles_x, ntiles, stride, bpx, bpt};
     const CamD cd{};
     int qrc = VHX_OK;
     // the frames' blocks over whole tiles of the list order (k_trace_primary), or flags in the flag order; a batch of
@@ -2958,14 +3035,16 @@ static int trace_batch(vhx_ctx *c, const vhx_camera *cams, uint32_t n, const vhx
             q0.zero = (uint32_t *)c->qctl.ptr + 16;
         else if (npass > 1)
             q0.flags = (uint8_t *)c->flags.ptr;
+        // everything the kernel would derive from the grid size, and its divisions, as constants
+        const BatchGrid bg = batch_grid((uint32_t)(nbf0 * n), n, (uint32_t)nbf0, bx, q0, lo, tb);
         if (fuse) {
             k_trace_primary_batch<BD, true><<<(unsigned)(nbf0 * n), 256, 0, c->stream>>>(
-                t, dcams, douts, (uint32_t)nbf0, bx, (uint32_t)npix, q0, lo, tb);
+                t, dcams, douts, (uint32_t)nbf0, bx, (uint32_t)npix, q0, bg, lo, tb, dstarts);
             qrc = launch_queue_passes<false, BD, false, true>(c, t, cd, src, OutD{}, 1, npass, nout, nbf0 * n,
                                                               P0_ORDERED, T ? 0u : W, H, n, qm);
         } else {
             k_trace_primary_batch<BD><<<(unsigned)(nbf0 * n), 256, 0, c->stream>>>(t, dcams, douts, (uint32_t)nbf0, bx,
-                                                                                   (uint32_t)npix, q0, lo, tb);
+                                                                                   (uint32_t)npix, q0, bg, lo, tb, dstarts);
             qrc = launch_queue_passes<false, BD>(c, t, cd, src, OutD{}, 1, npass, nout, nbf0 * n,
                                                  listed ? P0_ORDERED : P0_FLAGS, T ? 0u : W, H, n, qm);
         }
