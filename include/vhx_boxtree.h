@@ -8,6 +8,8 @@
  *   vhx_boxtree_insert         <- BoxTree::insert         (src/boxtree/update/insert.rs:21-30)
  *   vhx_boxtree_insert_at_lod  <- BoxTree::insert_at_lod  (src/boxtree/update/insert.rs:37-47)
  *   vhx_boxtree_update         <- BoxTree::update         (src/boxtree/update/insert.rs:53-62)
+ *   vhx_boxtree_clear          <- BoxTree::clear          (src/boxtree/update/clear.rs:16-22)
+ *   vhx_boxtree_clear_at_lod   <- BoxTree::clear_at_lod   (src/boxtree/update/clear.rs:23-338)
  *   vhx_boxtree_get            <- BoxTree::get            (src/boxtree/mod.rs:223-233)
  *   vhx_boxtree_simplify       <- BoxTree::simplify(ROOT, recursive) (src/boxtree/update/mod.rs:617-867)
  *   vhx_boxtree_flatten        <- BoxTreeGPUDataHandler::add_node/add_brick with every node resident
@@ -70,6 +72,12 @@ int vhx_boxtree_insert_at_lod(vhx_boxtree *tree, uint32_t x, uint32_t y, uint32_
                               uint32_t kind, uint32_t albedo, uint32_t data);
 int vhx_boxtree_update(vhx_boxtree *tree, uint32_t x, uint32_t y, uint32_t z, uint32_t kind, uint32_t albedo,
                        uint32_t data);
+/* Removal: the voxel at a position, or every voxel of the cube [position, position + clear_size) that lies in the tree.
+ * A position outside the tree returns VHX_E_TREE_INVALID_POSITION; clear_size 0 changes nothing. Emptied bricks and
+ * nodes are released (a node's pool key is handed out again by later inserts), occupied bits shrink, and with MIP maps
+ * on the MIPs of the nodes on the path follow. Where this differs from the reference is listed in docs/DESIGN_LOG.md. */
+int vhx_boxtree_clear(vhx_boxtree *tree, uint32_t x, uint32_t y, uint32_t z);
+int vhx_boxtree_clear_at_lod(vhx_boxtree *tree, uint32_t x, uint32_t y, uint32_t z, uint32_t clear_size);
 int vhx_boxtree_get(const vhx_boxtree *tree, uint32_t x, uint32_t y, uint32_t z, uint32_t *kind, uint32_t *albedo,
                     uint32_t *data);
 int vhx_boxtree_simplify(vhx_boxtree *tree, int recursive);

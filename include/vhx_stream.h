@@ -18,11 +18,18 @@
  *   vhx_stream_reload       <- BoxTreeGPUView::reload (view.rs:141-145)
  *   vhx_stream_view         host mirror of the device view (for checking; pointers valid until the next call)
  *
- * Tree changes: inserts and updates of the tree (vhx_boxtree_insert / _insert_at_lod / _update) made while a stream
- * exists are queued by the tree (the update trigger of BoxTreeGPUHost::new, src/raytracing/bevy/mod.rs:164-173) and
+ * Tree changes: inserts, updates and clears of the tree (vhx_boxtree_insert / _insert_at_lod / _update / _clear /
+ * _clear_at_lod) made while a stream exists are queued by the tree (the update trigger of BoxTreeGPUHost::new, src/raytracing/bevy/mod.rs:164-173) and
  * re-uploaded by the next vhx_stream_upload calls (handle_tree_updates, streaming/mod.rs:35-286: up to
  * node_uploads_per_frame changes per frame, ahead of the upload queue). One stream per tree receives them, like the
- * reference's single changes buffer. The tree and the context must outlive the stream; ctx = NULL keeps the view on
+ * reference's single changes buffer. Removal (no reference counterpart: its handle_tree_updates only notes that an
+ * "update might have been a clear operation"): the tree also reports every pool key it frees and every node simplify
+ * changes in place. At the start of an upload, before anything else, the stream drops what it holds for freed keys (the
+ * node slot, its child bricks, its MIP slot; the parent's child entry becomes VHX_EMPTY) and rewrites the changed nodes;
+ * a queued change's stack is followed only as far as the tree still links it; a brick that is no longer Parted gives its
+ * slot back. Contract: after any sequence of inserts, updates and clears, once `pending` is 0 the view traces exactly
+ * like the tree inside the streamed region, and released node and brick slots are reused (insert / clear cycles do not
+ * grow the view). The tree and the context must outlive the stream; ctx = NULL keeps the view on
  * the host only (vhx_stream_view), which is how the producer is tested without a GPU. Every frame's ranged writes go
  * to the device as one vhx_update_ranges call (stream-ordered, no host synchronisation).
  */
@@ -48,7 +55,7 @@ typedef struct vhx_stream_stats {
     uint64_t bricks_in_view;  /* brick capacity */
     uint64_t nodes_to_see;    /* nodes the viewport needs */
     uint64_t pending;         /* work left: nodes to see that are not resident + queued brick requests + queued tree
-                                 changes, + 1 until a
+                                 changes, freed keys and changed nodes not yet taken, + 1 until a
                                  complete walk cycle found nothing new (the node walk restarts from the root whenever
                                  it finishes, as in the reference, so a lost brick is requested on the next cycle) */
 } vhx_stream_stats;

@@ -150,6 +150,8 @@ SIGNATURES = [
     ("vhx_boxtree_insert", c_int, [c_void_p, c_u32, c_u32, c_u32, c_u32, c_u32, c_u32]),
     ("vhx_boxtree_insert_at_lod", c_int, [c_void_p, c_u32, c_u32, c_u32, c_u32, c_u32, c_u32, c_u32]),
     ("vhx_boxtree_update", c_int, [c_void_p, c_u32, c_u32, c_u32, c_u32, c_u32, c_u32]),
+    ("vhx_boxtree_clear", c_int, [c_void_p, c_u32, c_u32, c_u32]),
+    ("vhx_boxtree_clear_at_lod", c_int, [c_void_p, c_u32, c_u32, c_u32, c_u32]),
     ("vhx_boxtree_get", c_int, [c_void_p, c_u32, c_u32, c_u32, P(c_u32), P(c_u32), P(c_u32)]),
     ("vhx_boxtree_simplify", c_int, [c_void_p, c_int]),
     ("vhx_boxtree_info", c_int, [c_void_p, P(c_u32 * 5)]),

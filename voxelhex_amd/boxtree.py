@@ -7,6 +7,8 @@ this module keeps the reference's names, argument meaning and error behaviour:
     tree.insert(pos, entry)              BoxTree::insert         -> raises OctreeError.InvalidPosition
     tree.insert_at_lod(pos, size, entry) BoxTree::insert_at_lod
     tree.update(pos, entry)              BoxTree::update
+    tree.clear(pos)                      BoxTree::clear          -> raises OctreeError.InvalidPosition
+    tree.clear_at_lod(pos, size)         BoxTree::clear_at_lod
     tree.get(pos) -> BoxTreeEntry        BoxTree::get
     tree.get_by_ray(ray)                 BoxTree::get_by_ray (src/raytracing/cpu.rs:296), traced on the GPU
 """
@@ -434,6 +436,19 @@ class BoxTree:
     def update(self, position, data):
         x, y, z = _pos(position)
         _tree_check(N.lib().vhx_boxtree_update(self._h, x, y, z, *_entry_args(data)), f"{(x, y, z)}")
+        self._version += 1
+
+    def clear(self, position):
+        """BoxTree::clear (src/boxtree/update/clear.rs:16-18)."""
+        x, y, z = _pos(position)
+        _tree_check(N.lib().vhx_boxtree_clear(self._h, x, y, z), f"{(x, y, z)}")
+        self._version += 1
+
+    def clear_at_lod(self, position, clear_size):
+        """BoxTree::clear_at_lod (src/boxtree/update/clear.rs:23-338): removes the cube of edge `clear_size` at
+        `position`."""
+        x, y, z = _pos(position)
+        _tree_check(N.lib().vhx_boxtree_clear_at_lod(self._h, x, y, z, int(clear_size)), f"{(x, y, z)}")
         self._version += 1
 
     def get(self, position):

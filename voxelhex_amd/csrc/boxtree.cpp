@@ -400,7 +400,27 @@ void BoxTree::deallocate_children_of(size_t key) {  // detail.rs:352-370
             if (nodes.key_is_valid(c)) to_free.push_back(c);
     for (size_t c : to_free) {
         deallocate_children_of(c);
-        nodes.free(c);
+        free_node(c);
+    }
+    // "and set its children to 'No children'" (detail.rs:350): the reference's body leaves the list in place, so the
+    // node keeps naming freed keys, and once the pool hands such a key out again (ObjectPool::allocate takes the lowest
+    // free one) the node reaches an unrelated node through it. Removal makes that reuse common; the list is dropped.
+    nodes.get(key).has_children = false;
+}
+bool BoxTree::free_node(size_t key) {
+    if (!nodes.free(key)) return false;
+    if (track_changes > 0) freed_keys.push_back(key);
+    return true;
+}
+bool BoxTree::content_is_empty(const Node &n) const {  // NodeContent::is_empty, node.rs:376-421
+    switch (n.content) {
+        case Content::UniformLeaf: return brick_contains_nothing(n.bricks[0]);
+        case Content::Leaf:
+            for (const Brick &b : n.bricks)
+                if (!brick_contains_nothing(b)) return false;
+            return true;
+        case Content::Internal: return false;
+        default: return true;
     }
 }
 Brick BoxTree::try_brick_from_node(size_t key) const {  // detail.rs:340-349
@@ -423,7 +443,10 @@ std::array<std::vector<uint32_t>, kChildren> BoxTree::dilute_brick_data(const st
             // octant_in_sectants (src/spatial/math/mod.rs:56-59)
             const float *o = sectant_offset(s);
             float ox = o[0] * 2.f, oy = o[1] * 2.f, oz = o[2] * 2.f;
-            size_t oct = (size_t)(ox >= 1.f) + (size_t)(oz >= 1.f) * 2 + (size_t)(oy >= 1.f) * 4;
+            // Deviation: octant_in_sectants weighs z by 2 and y by 4, but it indexes a brick laid out by
+            // flat_projection (x + 2y + 4z), so a split uniform leaf came out with its y and z halves exchanged
+            // (seen as 128 wrong voxels by the dense-model test of tests/test_boxtree_clear_model.py)
+            size_t oct = (size_t)(ox >= 1.f) + (size_t)(oy >= 1.f) * 2 + (size_t)(oz >= 1.f) * 4;
             result[s].assign(n3, bdata[oct]);
         }
         return result;
@@ -476,14 +499,20 @@ void BoxTree::subdivide_leaf_to_nodes(size_t key, size_t target_sectant) {  // d
             bricks[s] = Brick{};  // std::mem::swap leaves BrickData::Empty behind
             if (!brick_contains_nothing(brick) || s == target_sectant)
                 new_children[s] = (uint32_t)nodes.push(empty_node());
+            // a brick that holds nothing but is not Empty (a Parted brick whose voxels were all cleared) got no child
+            // above; the reference indexes the pool with the empty marker then (detail.rs:273-293) and panics
+            if (new_children[s] == kEmpty32) continue;
             if (brick.kind == BrickKind::Solid) {
                 Node &c = nodes.get(new_children[s]);
                 c.occupied_bits = ~0ull;
                 c.content = Content::UniformLeaf;
                 c.bricks.assign(1, solid(brick.solid));
             } else if (brick.kind == BrickKind::Parted) {
-                // detail.rs:283-289 computes the occupancy of bricks[sectant] after the swap, i.e. of Empty -> 0
-                uint64_t occ = calculate_occupied_bits(bricks[s]);
+                // Deviation: detail.rs:283-289 computes the occupancy of bricks[sectant] after the swap, i.e. of Empty,
+                // so the new child holds voxels under occupied bits of 0. An insert only ever adds bits to that, but a
+                // clear recomputes the touched sectants alone, finds 0 and removes the node with the voxels it still
+                // holds. The occupancy is computed from the brick that moves into the child.
+                uint64_t occ = calculate_occupied_bits(brick);
                 Node &c = nodes.get(new_children[s]);
                 c.occupied_bits = occ;
                 c.content = Content::UniformLeaf;
@@ -599,7 +628,9 @@ bool BoxTree::leaf_update(bool overwrite, size_t key, const Cube &node_bounds, c
                     n.bricks = std::move(leaf);
                     return true;
                 }
-                break;  // falls through to the recursive call below (unreachable for insert: data is never empty)
+                // Deviation: empty data into an Empty uniform leaf (reachable from clear only) falls through to the
+                // recursive call of update/mod.rs:409-416 in the reference, which never ends; nothing changes here
+                return false;
             }
             if (mat.kind == BrickKind::Solid) {
                 uint32_t v = mat.solid;
@@ -643,13 +674,17 @@ bool BoxTree::leaf_update(bool overwrite, size_t key, const Cube &node_bounds, c
             }
         }
         case Content::Internal: {
-            node.has_children = false;  // children = NoChildren before the bricks are gathered (update/mod.rs:420)
+            // Deviation: the reference sets children = NoChildren before it gathers the children's bricks
+            // (update/mod.rs:420, "might induce data loss - see #69"), so every brick reads Empty and the child nodes
+            // stay allocated but unreachable: a voxel edit next to a brick-sized child node (insert_at_lod and clear
+            // make those) emptied the whole node. The bricks are gathered and the children freed first.
             std::vector<Brick> leaf(kChildren);
             for (size_t s = 0; s < kChildren; ++s) leaf[s] = try_brick_from_node(child(key, (uint8_t)s));
+            deallocate_children_of(key);
             Node &n = nodes.get(key);
+            n.has_children = false;
             n.content = Content::Leaf;
             n.bricks = std::move(leaf);
-            deallocate_children_of(key);
             return leaf_update(overwrite, key, node_bounds, target_bounds, tcs, position, size, tc);
         }
         case Content::Nothing: {
@@ -896,6 +931,212 @@ int BoxTree::insert_at_lod_internal(bool overwrite, U3 pos_u32, uint32_t insert_
     return 0;
 }
 
+// the six neighbours of post_process_node_insert / _clear: direction, and the CubeSides bit of the sibling facing back
+static const int kSiblingDirs[6][4] = {{-1, 0, 0, 5 /*Right*/}, {1, 0, 0, 4 /*Left*/},  {0, -1, 0, 2 /*Top*/},
+                                       {0, 1, 0, 3 /*Bottom*/}, {0, 0, -1, 1 /*Front*/}, {0, 0, 1, 0 /*Back*/}};
+
+int BoxTree::clear_at_lod(U3 pos_u32, uint32_t clear_size) {  // src/boxtree/update/clear.rs:23-338
+    const Cube root{f3(0.f, 0.f, 0.f), (float)boxtree_size};
+    const F3 position = from_u3(pos_u32);
+    if (!cube_contains(root, position)) return VHX_E_TREE_INVALID_POSITION;  // clear.rs:30-36
+    if (clear_size == 0) return 0;                                           // clear.rs:39-41
+
+    std::vector<std::pair<size_t, uint8_t>> node_stack{{0, sectant_for(root, position)}};
+    std::vector<Cube> bounds_stack{root};
+    std::vector<uint8_t> erased_whole_sectants, modified_bottom;
+    std::array<size_t, 3> actual_update_size{0, 0, 0};
+    bool updated = false;
+    const uint32_t empty = kEmpty32;  // empty_marker::<PaletteIndexValues>()
+    for (;;) {
+        const size_t cur = node_stack.back().first;
+        const uint8_t tcs = node_stack.back().second;
+        const Cube cb = bounds_stack.back();
+        const Cube tb = child_bounds_for(cb, tcs);
+        const size_t tck = child(cur, tcs);
+
+        // clear.rs:68-109: whole children of an Internal node (`position <= min_position` is V3c's derived order)
+        if (clear_size > 1 && tb.size <= (float)clear_size && lex_le(position, tb.min) &&
+            nodes.get(cur).content == Content::Internal) {
+            actual_update_size =
+                execute_for_relevant_sectants(cb, pos_u32, clear_size, [&](U3 pit, U3 uit, uint8_t cs, const Cube &ctb) {
+                    const U3 ctb_min = round_u3(ctb.min);
+                    const uint32_t csz = as_u32(ctb.size);
+                    if (pit.x == ctb_min.x && pit.y == ctb_min.y && pit.z == ctb_min.z && uit.x == csz && uit.y == csz &&
+                        uit.z == csz) {
+                        const size_t ck = child(cur, cs);
+                        if (nodes.key_is_valid(ck)) {  // an invalid key: the area is empty already
+                            updated = true;
+                            deallocate_children_of(ck);
+                            Node &c = nodes.get(ck);
+                            c.content = Content::Nothing;
+                            c.bricks.clear();
+                            c.has_children = false;
+                            erased_whole_sectants.push_back(cs);
+                        }
+                    }
+                });
+            break;
+        }
+
+        if (tb.size > (float)std::max(clear_size, brick_dim) || nodes.key_is_valid(tck)) {  // clear.rs:111-219
+            if (nodes.key_is_valid(tck)) {
+                node_stack.push_back({tck, sectant_for(tb, position)});
+                bounds_stack.push_back(tb);
+            } else {
+                const Node &cn = nodes.get(cur);
+                if (cn.content == Content::Leaf || cn.content == Content::UniformLeaf) {
+                    // clear.rs:130-181: the brick is indexed by `position - current_bounds.min_position` as it stands;
+                    // an index past the brick (the reference would panic) reads as "no match"
+                    const Brick &b = cn.content == Content::UniformLeaf ? cn.bricks[0] : cn.bricks[tcs];
+                    bool target_match = false;
+                    if (b.kind == BrickKind::Empty) {
+                        target_match = true;
+                    } else if (b.kind == BrickKind::Solid) {
+                        target_match = points_to_empty(b.solid);
+                    } else {
+                        const F3 d = sub(position, cb.min);
+                        const size_t f = flat_projection(as_usize(d.x), as_usize(d.y), as_usize(d.z), brick_dim);
+                        target_match = f < b.parted.size() && points_to_empty(b.parted[f]);
+                    }
+                    if (target_match || content_is_empty(cn)) break;  // clear.rs:182-192
+                    subdivide_leaf_to_nodes(cur, tcs);               // clear.rs:204-213
+                    node_stack.push_back({child(cur, tcs), sectant_for(tb, position)});
+                    bounds_stack.push_back(tb);
+                } else {
+                    break;  // clear.rs:214-218: no child there in the first place
+                }
+            }
+        } else {  // clear.rs:220-242
+            actual_update_size =
+                execute_for_relevant_sectants(cb, pos_u32, clear_size, [&](U3 pit, U3 uit, uint8_t cs, const Cube &ctb) {
+                    updated |= leaf_update(true, cur, cb, ctb, cs, pit, uit, empty);
+                    modified_bottom.push_back(cs);
+                });
+            break;
+        }
+    }
+    if (!updated) return 0;  // clear.rs:245-248
+
+    // post-processing, clear.rs:250-325
+    const std::vector<std::pair<size_t, uint8_t>> node_stack_clone = node_stack;
+    const std::vector<uint8_t> erased_bottom = erased_whole_sectants;
+    bool simplifyable = auto_simplify;
+    const size_t bottom_key = node_stack.back().first;
+    const uint8_t original = node_stack.back().second;
+    const Cube nbounds = bounds_stack.back();
+    for (uint8_t mbs : modified_bottom) {
+        const size_t ck = child(bottom_key, mbs);
+        if (nodes.key_is_valid(ck)) {  // the bottom update as a node
+            const Cube cbounds = child_bounds_for(nbounds, mbs);
+            node_stack.push_back({ck, sectant_for(cbounds, f3(std::fmax(position.x, cbounds.min.x),
+                                                              std::fmax(position.y, cbounds.min.y),
+                                                              std::fmax(position.z, cbounds.min.z)))});
+            post_process_node_clear(node_stack, cbounds, actual_update_size, pos_u32, clear_size, {});
+            node_stack.pop_back();
+        } else {  // the bottom update as a leaf
+            node_stack.back().second = mbs;
+            post_process_node_clear(node_stack, nbounds, actual_update_size, pos_u32, clear_size, {});
+            node_stack.back().second = original;
+        }
+        if (simplifyable) simplifyable &= simplify(ck, false);  // clear.rs:298-300
+    }
+    while (!node_stack.empty()) {  // clear.rs:304-325
+        const bool gone = post_process_node_clear(node_stack, bounds_stack.back(), actual_update_size, pos_u32,
+                                                  clear_size, std::move(erased_whole_sectants));
+        erased_whole_sectants.clear();
+        // Deviation: the reference hands the parent `bounds_stack.last().sectant_for(&position)` (clear.rs:313), the
+        // removed node's own target sectant; the parent frees `child(sectant)`, so it needs the sectant the removed
+        // node has in the parent, which is the parent's stack entry. With the reference's value the emptied node
+        // stays linked and an unrelated child is freed whenever the two sectants differ.
+        if (gone && node_stack.size() >= 2) erased_whole_sectants.push_back(node_stack[node_stack.size() - 2].second);
+        if (simplifyable) simplifyable = simplify(node_stack.back().first, true);  // clear.rs:318-321
+        node_stack.pop_back();
+        bounds_stack.pop_back();
+    }
+    ++edit_seq;
+    // clear.rs:327-335: the stack as cloned before post-processing, with the erased and the modified bottom sectants
+    // (the reference's `erased_whole_sectants` holds the root's post-processing result by now, clear.rs:305-316, not
+    // the sectants erased at the bottom; a follower of the change needs the latter)
+    if (track_changes > 0) {
+        std::vector<uint8_t> every = erased_bottom;
+        every.insert(every.end(), modified_bottom.begin(), modified_bottom.end());
+        changes.push_back(Change{node_stack_clone, std::move(every)});
+    }
+    return 0;
+}
+
+// clear.rs:343-478: connections, content, MIP, occupied and occlusion bits of a node after data was removed; true if
+// the node is empty now (or was removed before)
+bool BoxTree::post_process_node_clear(const std::vector<std::pair<size_t, uint8_t>> &node_stack_, const Cube &nb,
+                                      const std::array<size_t, 3> &aus, U3 clear_position, uint32_t clear_size,
+                                      std::vector<uint8_t> removed_children) {
+    const size_t key = node_stack_.back().first;
+    if (!nodes.key_is_valid(key)) return true;  // clear.rs:356-358
+
+    if (!removed_children.empty()) {  // clear.rs:362-406
+        std::vector<std::pair<size_t, uint8_t>> node_stack = node_stack_;
+        for (uint8_t cs : removed_children) {
+            const size_t ck = child(key, cs);
+            if (nodes.key_is_valid(ck)) {
+                if (nodes.get(ck).occupied_bits == ~0ull) {  // a full child no longer occludes its siblings
+                    const Cube cbn = child_bounds_for(nb, cs);
+                    node_stack.push_back({ck, sectant_for(cbn, f3(std::fmax((float)clear_position.x, cbn.min.x),
+                                                                  std::fmax((float)clear_position.y, cbn.min.y),
+                                                                  std::fmax((float)clear_position.z, cbn.min.z)))});
+                    for (const auto &dv : kSiblingDirs) {
+                        size_t sib;
+                        uint8_t ss;
+                        if (get_sibling_by_stack(dv[0], dv[1], dv[2], node_stack, sib, ss))
+                            nodes.get(sib).occlusion_bits &= (uint8_t)~(1u << dv[3]);
+                    }
+                    node_stack.pop_back();
+                }
+                free_node(ck);
+            }
+            // NodeData::clear_child (node.rs:241-248). Deviation: the reference drops the whole child list once
+            // exactly 8 entries are empty (an octree's count), which would unlink up to 56 live children of a
+            // 64-child node; the list is dropped when all 64 entries are empty
+            Node &n = nodes.get(key);
+            if (n.has_children) {
+                n.children[cs] = kEmpty32;
+                if (std::all_of(n.children.begin(), n.children.end(), [](uint32_t c) { return c == kEmpty32; }))
+                    n.has_children = false;
+            }
+        }
+    }
+
+    uint64_t occ = nodes.get(key).occupied_bits;
+    const size_t ns = as_usize(nb.size);
+    const U3 nb_min = round_u3(nb.min);
+    if (ns == aus[0] && ns == aus[1] && ns == aus[2] && nb_min.x == clear_position.x && nb_min.y == clear_position.y &&
+        nb_min.z == clear_position.z) {
+        occ = 0;
+    } else {
+        execute_for_relevant_sectants(nb, clear_position, clear_size, [&](U3, U3, uint8_t cs, const Cube &) {
+            if (node_empty_at(key, cs)) occ &= ~(1ull << cs);
+        });
+    }
+    if (occ == 0) {  // clear.rs:432-443
+        deallocate_children_of(key);
+        Node &n = nodes.get(key);
+        n.has_children = false;
+        n.content = Content::Nothing;
+        n.bricks.clear();
+        n.mip = Brick{};  // (an empty node has no MIP; only the root outlives this, the others are freed)
+    }
+    if (nodes.get(key).occupied_bits == ~0ull && occ != ~0ull) {  // clear.rs:456-473
+        for (const auto &dv : kSiblingDirs) {
+            size_t sib;
+            uint8_t ss;
+            if (get_sibling_by_stack(dv[0], dv[1], dv[2], node_stack_, sib, ss))
+                nodes.get(sib).occlusion_bits &= (uint8_t)~(1u << dv[3]);
+        }
+    }
+    nodes.get(key).occupied_bits = occ;
+    update_mip(key, nb, clear_position, true);  // clear.rs:475
+    return occ == 0;
+}
+
 bool BoxTree::simplify(size_t key, bool recursive) {  // src/boxtree/update/mod.rs:617-867
     if (!nodes.key_is_valid(key)) return false;
     ++edit_seq;
@@ -910,17 +1151,26 @@ bool BoxTree::simplify(size_t key, bool recursive) {  // src/boxtree/update/mod.
                     node.content = Content::Nothing;
                     node.bricks.clear();
                     node.has_children = false;
+                    note_touched(key);
                     return true;
                 }
                 return false;
             }
-            return brick_simplify(b);
+            if (!brick_simplify(b)) return false;
+            note_touched(key);
+            return true;
         }
         case Content::Leaf: {
             bool simplified = false, uniform_solid = true, have_usv = false;
             uint32_t usv = 0;
             for (Brick &b : node.bricks) {
-                simplified |= brick_simplify(b);
+                // a Parted brick that becomes Solid or Empty changes the node for a follower of the tree
+                if (b.kind == BrickKind::Parted && brick_simplify(b)) {
+                    simplified = true;
+                    note_touched(key);
+                } else {
+                    simplified |= brick_simplify(b);
+                }
                 if (uniform_solid) {
                     if (b.kind == BrickKind::Solid) {
                         if (have_usv) {
@@ -937,6 +1187,7 @@ bool BoxTree::simplify(size_t key, bool recursive) {  // src/boxtree/update/mod.
             if (uniform_solid) {
                 node.content = Content::UniformLeaf;
                 node.bricks.assign(1, solid(usv));
+                note_touched(key);
                 return true;
             }
             if (brick_dim == 1) return false;  // update/mod.rs:721-723 (even if bricks were simplified)
@@ -971,12 +1222,14 @@ bool BoxTree::simplify(size_t key, bool recursive) {  // src/boxtree/update/mod.
                 node.content = Content::UniformLeaf;
                 node.bricks.assign(1, parted(std::move(unified)));
                 simplified = true;
+                note_touched(key);
             }
             return simplified;
         }
         case Content::Internal: {
             if (node.occupied_bits == 0 || !node.has_children) {
                 node.content = Content::Nothing;
+                note_touched(key);
                 return true;
             }
             std::array<uint32_t, kChildren> ck = node.children;
@@ -1139,7 +1392,8 @@ bool BoxTree::albedo_of(uint32_t v, uint32_t &albedo) const {
     return true;
 }
 
-void BoxTree::update_mip(size_t key, const Cube &nb, U3 position) {  // src/boxtree/mipmap.rs:42-338
+void BoxTree::update_mip(size_t key, const Cube &nb, U3 position, bool erase_unsampled) {
+    // src/boxtree/mipmap.rs:42-338
     if (!mip_strategy.enabled) return;
     const Content content = nodes.get(key).content;
     if (content == Content::Nothing) return;
@@ -1148,7 +1402,22 @@ void BoxTree::update_mip(size_t key, const Cube &nb, U3 position) {  // src/boxt
         return;
     }
     uint32_t color = 0;
-    if (mip_sample(key, nb, position, color)) mip_store(key, nb, position, color);
+    if (mip_sample(key, nb, position, color)) {
+        mip_store(key, nb, position, color);
+        return;
+    }
+    if (!erase_unsampled) return;
+    // Deviation (clear path only): the reference leaves the cell alone when the resampling finds nothing
+    // (mipmap.rs:306-310), so the colour of voxels that were cleared away would stay in the MIP. The cell is emptied,
+    // and a MIP without any cell left is Empty again, which is what recalculate_mips builds for the same tree.
+    Brick &mip = nodes.get(key).mip;
+    if (mip.kind != BrickKind::Parted) return;
+    const auto mi = matrix_index_for(nb, position, brick_dim);
+    if (mi[0] >= brick_dim || mi[1] >= brick_dim || mi[2] >= brick_dim) return;
+    mip.parted[flat_projection(mi[0], mi[1], mi[2], brick_dim)] = kEmpty32;
+    for (uint32_t v : mip.parted)
+        if (v != kEmpty32) return;
+    mip = Brick{};
 }
 
 // mipmap.rs:42-270: the sampled colour of the MIP cell `position` falls in (Leaf / Internal nodes only)

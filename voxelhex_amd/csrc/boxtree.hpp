@@ -5,6 +5,7 @@
 //   ObjectPool                 src/object_pool.rs:51-266 (same key allocation, so node keys match the reference)
 //   BoxTree::new / get         src/boxtree/mod.rs:188-317
 //   insert / insert_at_lod     src/boxtree/update/insert.rs:21-407, post_process_node_insert 411-495
+//   clear / clear_at_lod       src/boxtree/update/clear.rs:16-338, post_process_node_clear 343-478
 //   add_to_palette             src/boxtree/update/mod.rs:39-120
 //   leaf_update                src/boxtree/update/mod.rs:144-464
 //   dilute_brick_data          src/boxtree/update/mod.rs:478-555, update_brick 564-603
@@ -125,6 +126,8 @@ class BoxTree {
     int insert(U3 pos, Entry e) { return insert_at_lod_internal(true, pos, 1, e); }
     int insert_at_lod(U3 pos, uint32_t size, Entry e) { return insert_at_lod_internal(true, pos, size, e); }
     int update(U3 pos, Entry e) { return insert_at_lod_internal(false, pos, 1, e); }
+    int clear(U3 pos) { return clear_at_lod(pos, 1); }  // clear.rs:16-18
+    int clear_at_lod(U3 pos, uint32_t clear_size);
     uint32_t get_raw(U3 pos) const;
     Entry get(U3 pos) const;
     Entry entry_of(uint32_t value) const;
@@ -134,7 +137,8 @@ class BoxTree {
     void switch_albedo_mip_maps(bool enabled);
     void recalculate_mips();
     void recalculate_mip(size_t node_key, const Cube &node_bounds);
-    void update_mip(size_t node_key, const Cube &node_bounds, U3 position);
+    // erase_unsampled (the clear path): a cell whose resampling finds nothing is emptied instead of kept (boxtree.cpp)
+    void update_mip(size_t node_key, const Cube &node_bounds, U3 position, bool erase_unsampled = false);
     // the two halves of update_mip: the resampling (reads the tree only; false for None) and the palette match + store
     bool mip_sample(size_t node_key, const Cube &node_bounds, U3 position, uint32_t &color) const;
     void mip_store(size_t node_key, const Cube &node_bounds, U3 position, uint32_t color);
@@ -155,6 +159,16 @@ class BoxTree {
     };
     mutable std::deque<Change> changes;
     mutable int track_changes = 0;
+    // pool keys freed while a stream tracks the tree (clears, and the frees of leaf_update / simplify), in the order
+    // they were freed. A key may be handed out again by the pool before the stream reads the queue: the stream drops
+    // whatever it holds for these keys before it processes a change (stream.cpp, drop_freed_keys)
+    mutable std::deque<size_t> freed_keys;
+    // nodes simplify changed in place while a stream tracks the tree (a recursive simplify reaches nodes that are on no
+    // queued change's stack); may hold a key more than once
+    mutable std::deque<size_t> touched_keys;
+    void note_touched(size_t key) {
+        if (track_changes > 0 && (touched_keys.empty() || touched_keys.back() != key)) touched_keys.push_back(key);
+    }
     // bumped by every structural edit (update_at_lod, simplify), tracked or not: a stream's cached view walk is valid
     // only for the edit_seq it was made on (vhx_stream rebuild)
     uint64_t edit_seq = 0;
@@ -185,6 +199,11 @@ class BoxTree {
     uint32_t leaf_value(const struct Node &n, const Cube &nb, U3 pos) const;
 
     int insert_at_lod_internal(bool overwrite_if_empty, U3 pos, uint32_t insert_size, Entry e);
+    bool post_process_node_clear(const std::vector<std::pair<size_t, uint8_t>> &node_stack, const Cube &node_bounds,
+                                 const std::array<size_t, 3> &aus, U3 clear_position, uint32_t clear_size,
+                                 std::vector<uint8_t> removed_children);
+    bool free_node(size_t key);  // ObjectPool::free, recorded in freed_keys while a stream tracks the tree
+    bool content_is_empty(const Node &n) const;
     void post_process_node_insert(const std::vector<std::pair<size_t, uint8_t>> &node_stack, const Cube &node_bounds,
                                   const std::array<size_t, 3> &aus, U3 pos, uint32_t insert_size);
     bool get_sibling_by_stack(int dx, int dy, int dz, const std::vector<std::pair<size_t, uint8_t>> &node_stack,

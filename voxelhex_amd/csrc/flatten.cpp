@@ -497,6 +497,14 @@ int vhx_boxtree_update(vhx_boxtree *tree, uint32_t x, uint32_t y, uint32_t z, ui
     if (!tree || kind > VHX_ENTRY_COMPLEX) return VHX_E_INVALID_ARG;
     return tree->tree->update(U3{x, y, z}, Entry{kind, albedo, data});
 }
+int vhx_boxtree_clear(vhx_boxtree *tree, uint32_t x, uint32_t y, uint32_t z) {
+    if (!tree) return VHX_E_INVALID_ARG;
+    return tree->tree->clear(U3{x, y, z});
+}
+int vhx_boxtree_clear_at_lod(vhx_boxtree *tree, uint32_t x, uint32_t y, uint32_t z, uint32_t clear_size) {
+    if (!tree) return VHX_E_INVALID_ARG;
+    return tree->tree->clear_at_lod(U3{x, y, z}, clear_size);
+}
 int vhx_boxtree_get(const vhx_boxtree *tree, uint32_t x, uint32_t y, uint32_t z, uint32_t *kind, uint32_t *albedo,
                     uint32_t *data) {
     if (!tree || !kind || !albedo || !data) return VHX_E_INVALID_ARG;

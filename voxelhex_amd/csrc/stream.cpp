@@ -22,6 +22,9 @@
 // Tree-change propagation: inserts and updates made to the tree while a stream tracks it are queued by the tree
 // (BoxTree::changes, the update trigger of BoxTreeGPUHost::new) and re-uploaded by handle_tree_updates
 // (streaming/mod.rs:35-286) at the start of the next upload frames, before the regular upload queue.
+// Removal (clear, clear_at_lod; no reference counterpart, see "removal" below and docs/DESIGN_LOG.md §10c): the tree
+// also reports the pool keys it frees and the nodes simplify changes in place; what the view holds for a freed key is
+// dropped before anything else reads the tree by key, and a brick that is no longer Parted gives its slot back.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -224,7 +227,11 @@ struct vhx_stream {
     bool walk_started = false;
 
     ~vhx_stream() {
-        if (tree && --tree->track_changes == 0) tree->changes.clear();
+        if (tree && --tree->track_changes == 0) {
+            tree->changes.clear();
+            tree->freed_keys.clear();
+            tree->touched_keys.clear();
+        }
     }
     uint32_t bd() const { return tree->brick_dim; }
     uint32_t max_mip_level() const {  // boxtree/mod.rs:320-324
@@ -804,6 +811,119 @@ struct vhx_stream {
         return false;
     }
 
+    // ------------------------------------------------------------------------------------- removal (no reference)
+    // whether the tree holds a Parted brick for owner (node, sectant)
+    bool has_parted(size_t key, uint8_t s) const {
+        if (!key_valid(key)) return false;
+        const Node &n = node(key);
+        if (n.content == Content::UniformLeaf) return s == 0 && n.bricks[0].kind == BrickKind::Parted;
+        if (n.content == Content::Leaf) return n.bricks[s].kind == BrickKind::Parted;
+        return false;
+    }
+    // A brick slot is owned by (node, sectant). Where the node has no Parted brick at the sectant any more (cleared to
+    // Empty, simplified to Solid, the node's content changed kind), the slot is released; the node's child entries
+    // are rewritten by the caller (add_node)
+    void release_stale_bricks(size_t key) {
+        Owned o;
+        o.kind = 1;
+        o.node = (uint32_t)key;
+        for (uint8_t s = 0; s < kChildren; ++s) {
+            o.sectant = s;
+            auto it = brick_by_owner.find(o.key());
+            if (it != brick_by_owner.end() && !has_parted(key, s)) owner_remove_index(it->second);
+        }
+    }
+    // the voxels of every brick slot the node owns are written again (the node's bricks may all have changed: a
+    // uniform leaf diluted into 64 bricks, 64 bricks unified into one)
+    void reupload_owned_bricks(size_t key, std::vector<CacheUpdate> &updates) {
+        Owned o;
+        o.kind = 1;
+        o.node = (uint32_t)key;
+        CacheUpdate u;
+        for (uint8_t s = 0; s < kChildren; ++s) {
+            o.sectant = s;
+            auto it = brick_by_owner.find(o.key());
+            if (it != brick_by_owner.end()) u.brick_updates.push_back({it->second, brick_by_index[it->second]});
+        }
+        if (!u.brick_updates.empty()) updates.push_back(std::move(u));
+    }
+    // Everything the view holds for pool keys the tree freed: the node's slot (its parent's child entry becomes empty),
+    // its child bricks and its MIP slot. Runs before anything else reads the tree by key: a freed key may be live again
+    // as another node by now, and nothing the view holds for it describes that node. No tree node is read here.
+    void drop_freed_keys(std::vector<CacheUpdate> &updates) {
+        while (!tree->freed_keys.empty()) {
+            const size_t key = tree->freed_keys.front();
+            tree->freed_keys.pop_front();
+            Owned o;
+            o.node = (uint32_t)key;
+            o.kind = 2;
+            auto mo = brick_by_owner.find(o.key());
+            if (mo != brick_by_owner.end()) owner_remove_index(mo->second);
+            o.kind = 1;
+            for (uint8_t s = 0; s < kChildren; ++s) {
+                o.sectant = s;
+                auto it = brick_by_owner.find(o.key());
+                if (it != brick_by_owner.end()) owner_remove_index(it->second);
+            }
+            nodes_to_see.erase(key);
+            auto mi = meta_by_key.find(key);
+            if (mi == meta_by_key.end()) continue;
+            const size_t m = mi->second;
+            CacheUpdate u;
+            auto p = node_index_vs_parent.find(m);
+            if (p != node_index_vs_parent.end()) {
+                const size_t off = p->second.first * kChildren + p->second.second;
+                if (node_children[off] == (uint32_t)m) {
+                    node_children[off] = kEmpty;
+                    u.modified_nodes.push_back({p->second.first, 1ull << p->second.second});
+                }
+                node_index_vs_parent.erase(p);
+            }
+            set_resident(key, false);
+            meta_by_key.erase(mi);
+            key_by_meta.erase(m);
+            node_type[m] = VHX_NODE_NOTHING;
+            node_ocbits[m] = 0;
+            std::fill(node_children.begin() + (ptrdiff_t)(m * kChildren),
+                      node_children.begin() + (ptrdiff_t)((m + 1) * kChildren), kEmpty);
+            set_mip(m, kEmpty);
+            u.modified_nodes.push_back({m, ~0ull});
+            updates.push_back(std::move(u));
+            view_walk.valid = false;
+        }
+    }
+    // a resident node the tree changed in place (simplify) is written again from the tree, through its parent's entry
+    // the view ran out of room for `key`: it goes back to the front of the queue, so the frame after the resize
+    // rewrites it (a resize keeps the view's content; nothing else would ever visit the node again)
+    bool requeue_touched(size_t key) {
+        tree->touched_keys.push_front(key);
+        return false;
+    }
+    bool refresh_touched(std::vector<CacheUpdate> &updates) {
+        std::unordered_set<size_t> seen;
+        while (!tree->touched_keys.empty()) {
+            const size_t key = tree->touched_keys.front();
+            tree->touched_keys.pop_front();
+            if (!seen.insert(key).second || !key_valid(key)) continue;
+            auto mi = meta_by_key.find(key);
+            if (mi == meta_by_key.end()) continue;
+            CacheUpdate u;
+            if (key == 0) {
+                if (!add_node(0, (uint8_t)kChildren, u)) return requeue_touched(key);
+            } else {
+                auto p = node_index_vs_parent.find(mi->second);
+                if (p == node_index_vs_parent.end()) continue;
+                auto pk = key_by_meta.find(p->second.first);
+                if (pk == key_by_meta.end() || !key_valid(pk->second) || child(pk->second, p->second.second) != key)
+                    continue;  // no longer that parent's child: a queued change or a freed key covers it
+                if (!add_node(pk->second, p->second.second, u)) return requeue_touched(key);
+            }
+            updates.push_back(std::move(u));
+            reupload_owned_bricks(key, updates);
+        }
+        return true;
+    }
+
     // ------------------------------------------------------------------------------------------ add_node
     bool add_node(size_t parent_key, uint8_t target_sectant, CacheUpdate &upd) {  // cache.rs:188-455
         const size_t key = target_sectant < kChildren ? child(parent_key, target_sectant) : 0;
@@ -822,6 +942,7 @@ struct vhx_stream {
             auto m = erase_node_child(robbed_parent.first, robbed_parent.second);
             upd.modified_nodes.insert(upd.modified_nodes.end(), m.begin(), m.end());
         }
+        release_stale_bricks(key);
         const Node &n = node(key);
         node_type[idx] = n.content == Content::Leaf          ? VHX_NODE_LEAF
                          : n.content == Content::UniformLeaf ? VHX_NODE_UNIFORM_LEAF
@@ -871,6 +992,9 @@ struct vhx_stream {
 
     // ----------------------------------------------------------------------------------------- add_brick
     bool add_brick(const Owned &req, CacheUpdate &upd) {  // cache.rs:575-716
+        // a request queued before an edit emptied the brick, or freed its node (whose key may be another node's by
+        // now): no slot is taken, or the node's child entry would point at voxels nothing writes
+        if (req.kind == 1 && !has_parted(req.node, req.sectant)) return true;
         size_t bi;
         if (!first_available_brick((float)tree->brick_dim, bi)) return false;
         auto prev = brick_by_index.find(bi);
@@ -1075,23 +1199,57 @@ struct vhx_stream {
                 updates.push_back(std::move(u));
             }
             if (!add_mip(0)) return re_evaluate_view_size();
-            const size_t parent_key = ch.node_stack.back().first;
+            // Deviation (removal): a change's stack is the edit's access path as it was before the edit's
+            // post-processing. A clear frees nodes at the end of it, and a later edit may have freed more or have been
+            // handed a freed key for another node, so the stack is followed from the root only while each entry is
+            // still the child its predecessor names in the tree as it is now. What lies past that point is gone (its
+            // keys came through freed_keys) or belongs to a later change.
+            size_t live = 0;
+            for (size_t i = 0; i < ch.node_stack.size(); ++i) {
+                const size_t k = ch.node_stack[i].first;
+                const bool linked = i == 0 ? k == 0
+                                           : child(ch.node_stack[i - 1].first, ch.node_stack[i - 1].second) == k;
+                if (!linked || !key_valid(k)) break;
+                live = i + 1;
+            }
+            if (live == 0) continue;
+            const bool whole_stack = live == ch.node_stack.size();
+            const size_t parent_key = ch.node_stack[live - 1].first;
             Cube node_bounds{f3(0.f, 0.f, 0.f), (float)tree->boxtree_size};
-            for (const auto &e : ch.node_stack) nodes_to_see.insert(e.first);
+            for (size_t i = 0; i < live; ++i) nodes_to_see.insert(ch.node_stack[i].first);
             // the set now holds more than a walk's: the next rebuild is a full one; the tree changed: so may the
             // levels of its Internal nodes
             view_walk.valid = false;
             view_walk.mip1_internal = -1;
-            for (const auto &e : ch.node_stack) {
+            for (size_t i = 0; i < live; ++i) {
+                const auto &e = ch.node_stack[i];
                 size_t ck;
                 if (valid_child(e.first, e.second, ck)) {  // BoxTree::valid_child_for
                     CacheUpdate u;
                     if (!add_node(e.first, e.second, u)) return re_evaluate_view_size();
                     updates.push_back(std::move(u));
                     if (!add_mip(ck)) return re_evaluate_view_size();
+                    if (i + 1 == live) reupload_owned_bricks(ck, updates);
                 }
                 node_bounds = child_bounds_for(node_bounds, e.second);
             }
+            // the bottom node's other changed sectants: a child node there that is resident is written again (an edit
+            // over several sectants changes or empties children beside the one on the stack)
+            if (whole_stack && node(parent_key).content == Content::Internal)
+                for (uint8_t sec : ch.updated_sectants) {
+                    size_t ck;
+                    if (sec >= kChildren || sec == ch.node_stack.back().second || !valid_child(parent_key, sec, ck) ||
+                        !meta_by_key.count(ck))
+                        continue;
+                    CacheUpdate u;
+                    if (!add_node(parent_key, sec, u)) return re_evaluate_view_size();
+                    updates.push_back(std::move(u));
+                    if (!add_mip(ck)) return re_evaluate_view_size();
+                    reupload_owned_bricks(ck, updates);
+                }
+            // every brick the bottom node still owns is written again: its bricks may all have changed (a uniform
+            // leaf diluted into a leaf keeps its owner (node, 0) for another brick), not only the updated sectants
+            reupload_owned_bricks(parent_key, updates);
             // the bottom node's bricks: re-upload the resident ones, request slots for the others. Deviation: a
             // sectant whose brick is not Parted (the reference only debug-asserts that it is) is skipped; add_node
             // above already wrote its Solid / Empty descriptor
@@ -1115,7 +1273,7 @@ struct vhx_stream {
                 } else {
                     fresh.push_back(o);
                 }
-            } else if (pn.content == Content::Leaf) {
+            } else if (pn.content == Content::Leaf && whole_stack) {  // (a cut stack's sectants are another node's)
                 for (uint8_t sec : ch.updated_sectants) {
                     if (sec >= kChildren || pn.bricks[sec].kind != BrickKind::Parted) continue;
                     const Owned o = brick_owner(sec, child_bounds_for(node_bounds, sec));
@@ -1260,8 +1418,11 @@ struct vhx_stream {
     int collect_frame() {  // streaming/mod.rs:420-635
         last_nodes = last_bricks = last_bytes = 0;
         if (resize) return VHX_E_CAPACITY;
-        apply_pending_rebuild();
         std::vector<CacheUpdate> updates;
+        // removal: what the tree freed leaves the view before anything reads the tree by key (drop_freed_keys); nodes
+        // simplify changed in place are written again. Neither is rate-limited: both only touch resident slots.
+        drop_freed_keys(updates);
+        apply_pending_rebuild();
         // streaming::upload (streaming/mod.rs:446-457): a reloading view runs the upload queue; otherwise queued tree
         // changes go first, and the upload queue runs in a frame without any
         bool fits;
@@ -1269,9 +1430,11 @@ struct vhx_stream {
         const auto t0 = std::chrono::steady_clock::now();
 #endif
         if (reload) {
+            tree->touched_keys.clear();  // nothing is resident: the upload queue reads every node afresh
             fits = process(updates);
         } else {
-            fits = handle_tree_updates(updates, node_uploads_per_frame);
+            fits = refresh_touched(updates) || re_evaluate_view_size();
+            if (fits) fits = handle_tree_updates(updates, node_uploads_per_frame);
             if (fits && updates.empty()) fits = process(updates);
         }
 #ifdef VHX_STREAM_TIMING
@@ -1302,7 +1465,9 @@ struct vhx_stream {
             for (const auto &bu : u.brick_updates) {
                 const Owned &o = bu.second;
                 if (o.kind != 1 && !(o.kind == 2 && stream_mips())) continue;
+                if (!key_valid(o.node)) continue;  // freed by an edit later in the queue
                 const Node &n = node(o.node);
+                if (o.kind == 1 && !has_parted(o.node, o.sectant)) continue;
                 const Brick &b = o.kind == 2 ? n.mip : n.content == Content::UniformLeaf ? n.bricks[0] : n.bricks[o.sectant];
                 if (b.kind != BrickKind::Parted) continue;
                 std::copy(b.parted.begin(), b.parted.end(), voxels.begin() + (ptrdiff_t)(bu.first * n3));
@@ -1417,8 +1582,8 @@ int vhx_stream_upload_frames(vhx_stream *s, uint32_t frames, vhx_stream_stats *s
         stats->bricks_in_view = s->bricks_in_view;
         stats->nodes_to_see = s->nodes_to_see.size();
         const uint64_t missing = s->nodes_to_see.size() - s->nodes_to_see.n_resident;
-        stats->pending = missing + s->bricks_to_upload.size() + s->tree->changes.size() +
-                         (s->last_cycle_work == 0 ? 0u : 1u);
+        stats->pending = missing + s->bricks_to_upload.size() + s->tree->changes.size() + s->tree->freed_keys.size() +
+                         s->tree->touched_keys.size() + (s->last_cycle_work == 0 ? 0u : 1u);
     }
     return rc;
 }
