@@ -197,6 +197,22 @@ int vhx_upload_tree(vhx_ctx *ctx, const vhx_tree_desc *tree);
  * the GPU, or another device's copy where peer access is enabled): device-to-device copies on the context's stream,
  * then the derived layout. The receive half of vhx_mgpu_broadcast_tree, which fills the same buffers by ncclBroadcast. */
 int vhx_upload_tree_device(vhx_ctx *ctx, const vhx_tree_desc *tree);
+/* A dense voxel grid: the input of the bulk builders (vhx_dense_build in vhx_boxtree.h on the host, vhx_build_tree_dense
+ * on the GPU). The tree built from it is the one BoxTree::insert of every voxel in x-outer, y, z-inner order gives. */
+typedef struct vhx_dense_desc {
+    uint32_t boxtree_size, brick_dim;   /* validity rules of BoxTree::new */
+    uint32_t gx, gy, gz;                /* grid extents, 1..boxtree_size each; the grid sits at the tree's origin */
+    uint32_t reserved0;
+    const uint32_t *albedo;             /* voxel (x,y,z) at albedo[((uint64_t)z*gy + y)*gx + x], packed r|g<<8|b<<16|a<<24;
+                                           alpha byte 0 = no voxel (BoxTreeEntry::is_none of a Visual entry) */
+} vhx_dense_desc;
+/* Builds the canonical flattened tree of `grid` on the GPU and makes it the context's uploaded tree: the same seven
+ * buffers and counts as vhx_dense_build + vhx_upload_tree, bit for bit. on_device = 1: grid->albedo is device memory
+ * (read in place, never written); 0: host memory, copied to the device first. The build runs on the context's stream and
+ * the call returns when the tree is ready. Ordered like an upload (owner context only, VHX_E_STATE on a shared one;
+ * shared contexts trace the new tree afterwards), and like an upload it disables node MIPs. VHX_E_CAPACITY for more than
+ * 65,535 distinct colours or 2^31 bricks or more; a failing build leaves the context's previous tree as it was. */
+int vhx_build_tree_dense(vhx_ctx *ctx, const vhx_dense_desc *grid, int on_device);
 #define VHX_BUF_NODE_TYPE 0
 #define VHX_BUF_NODE_OCBITS 1
 #define VHX_BUF_NODE_CHILDREN 2
@@ -230,6 +246,11 @@ int vhx_update_ranges(vhx_ctx *ctx, const vhx_range *ranges, uint32_t n);
 #define VHX_DERIVED_NODE_HDR 0
 #define VHX_DERIVED_BRICK_OCC 1
 int vhx_read_derived(vhx_ctx *ctx, int which, uint64_t elem_offset, uint64_t elem_count, void *dst);
+/* The uploaded tree's sizes and counts (array pointers NULL). VHX_E_STATE before any upload. */
+int vhx_tree_counts(const vhx_ctx *ctx, vhx_tree_desc *counts);
+/* Copies elements [elem_offset, elem_offset+elem_count) of raw buffer VHX_BUF_* to host memory (the inverse of
+ * vhx_update_range); VHX_E_CAPACITY past the end. Stream-ordered, returns after the copy completed. */
+int vhx_read_range(vhx_ctx *ctx, int buffer_id, uint64_t elem_offset, uint64_t elem_count, void *dst);
 /* Device bytes held by the uploaded tree. */
 int vhx_tree_device_bytes(const vhx_ctx *ctx, uint64_t *bytes);
 

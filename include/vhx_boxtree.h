@@ -24,6 +24,7 @@
  *                                 (src/raytracing/bevy/types.rs:245-247) stand in for the missing children
  *   vhx_scene_build            <- bulk builder producing exactly the flattened tree that inserting a procedural
  *                                 scene voxel by voxel (x, then y, then z loops) would produce
+ *   vhx_dense_build            <- the same for a caller's dense voxel grid (vhx_dense_desc, vhx.h)
  *
  * Tree type parameter: T = u32 (the reference default, BoxTree<T = u32>, src/boxtree/types.rs:219).
  */
@@ -132,6 +133,16 @@ int vhx_scene_build_lod(uint32_t scene, uint32_t size, uint32_t brick_dim, uint6
  * nodes the reference would skip) and MIP maps (off; vhx_boxtree_switch_mips builds them). */
 int vhx_scene_build_tree(uint32_t scene, uint32_t size, uint32_t brick_dim, uint64_t seed, int threads,
                          vhx_boxtree **out);
+/* The bulk builder for a caller's dense grid (vhx_dense_desc, vhx.h): the flattened tree that inserting every voxel of
+ * the grid as a Visual entry (x outer, then y, z inner; voxels of alpha 0 skipped) and flattening would give -- only
+ * Parted bricks, no solid values, the colour palette in first-appearance order of that loop, no data palette.
+ * Sizes are refused as vhx_boxtree_new refuses them; a null grid or an extent of 0 or above boxtree_size:
+ * VHX_E_INVALID_ARG; more than 65,535 distinct colours (the palette index has 16 bits, 0xFFFF = none) or 2^31 bricks or
+ * more: VHX_E_CAPACITY. */
+int vhx_dense_build(const vhx_dense_desc *grid, int threads, vhx_flat **out);
+/* The host BoxTree of that image (as vhx_scene_build_tree: occlusion bits and MIP maps not restored); inserts, clears,
+ * MIPs and a stream continue from it. */
+int vhx_dense_build_tree(const vhx_dense_desc *grid, int threads, vhx_boxtree **out);
 int vhx_flat_node_mips(const vhx_flat *flat, const uint32_t **node_mips, uint32_t *count);
 /* Fills *desc with pointers into the flat object (valid until vhx_flat_free). */
 int vhx_flat_desc(const vhx_flat *flat, vhx_tree_desc *desc);

@@ -57,6 +57,11 @@ class TreeDesc(ctypes.Structure):
     ]
 
 
+class DenseDesc(ctypes.Structure):  # vhx_dense_desc
+    _fields_ = [("boxtree_size", c_u32), ("brick_dim", c_u32), ("gx", c_u32), ("gy", c_u32), ("gz", c_u32),
+                ("reserved0", c_u32), ("albedo", c_void_p)]
+
+
 class Range(ctypes.Structure):
     _fields_ = [("buffer_id", ctypes.c_int32), ("reserved0", c_u32), ("elem_offset", c_u64), ("elem_count", c_u64),
                 ("src", c_void_p)]
@@ -107,6 +112,9 @@ SIGNATURES = [
     ("vhx_set_tuning", c_int, [c_void_p, ctypes.c_char_p]),
     ("vhx_upload_tree", c_int, [c_void_p, P(TreeDesc)]),
     ("vhx_upload_tree_device", c_int, [c_void_p, P(TreeDesc)]),
+    ("vhx_build_tree_dense", c_int, [c_void_p, P(DenseDesc), c_int]),
+    ("vhx_tree_counts", c_int, [c_void_p, P(TreeDesc)]),
+    ("vhx_read_range", c_int, [c_void_p, c_int, c_u64, c_u64, c_void_p]),
     ("vhx_set_node_mips", c_int, [c_void_p, c_void_p, c_u32]),
     ("vhx_update_range", c_int, [c_void_p, c_int, c_u64, c_u64, c_void_p]),
     ("vhx_update_ranges", c_int, [c_void_p, c_void_p, c_u32]),
@@ -176,6 +184,8 @@ SIGNATURES = [
     ("vhx_scene_build", c_int, [c_u32, c_u32, c_u32, c_u64, c_int, P(c_void_p)]),
     ("vhx_scene_build_lod", c_int, [c_u32, c_u32, c_u32, c_u64, c_int, c_u32, P(c_void_p)]),
     ("vhx_scene_build_tree", c_int, [c_u32, c_u32, c_u32, c_u64, c_int, P(c_void_p)]),
+    ("vhx_dense_build", c_int, [P(DenseDesc), c_int, P(c_void_p)]),
+    ("vhx_dense_build_tree", c_int, [P(DenseDesc), c_int, P(c_void_p)]),
     ("vhx_flat_desc", c_int, [c_void_p, P(TreeDesc)]),
     ("vhx_boxtree_switch_mips", c_int, [c_void_p, c_int]),
     ("vhx_boxtree_set_mip_method", c_int, [c_void_p, c_u32, c_u32, c_f32]),

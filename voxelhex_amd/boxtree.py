@@ -256,6 +256,57 @@ class _OwnedBuffer:
                 "version": 3}
 
 
+TREE_ARRAYS = (("node_type", np.uint32), ("node_ocbits", np.uint64), ("node_children", np.uint32),
+               ("voxels", np.uint32), ("solid_values", np.uint32), ("color_palette", np.uint32),
+               ("data_palette", np.uint32))  # in VHX_BUF_* order
+
+
+def _dense_desc(grid, size, brick_dim):
+    """(vhx_dense_desc, the array it points into) of a numpy grid of shape (gz, gy, gx), dtype uint32."""
+    g = np.asarray(grid)
+    if g.ndim != 3 or g.dtype != np.uint32:
+        raise TypeError("a dense grid is a uint32 array of shape (gz, gy, gx)")
+    g = np.ascontiguousarray(g)
+    d = N.DenseDesc()
+    d.boxtree_size, d.brick_dim = int(size), int(brick_dim)
+    d.gz, d.gy, d.gx = (int(v) for v in g.shape)
+    d.albedo = g.ctypes.data
+    return d, g
+
+
+class TreeImage:
+    """A flattened tree held in numpy arrays (Raytracer.download): the seven arrays and counts of a vhx_tree_desc,
+    under FlatTree's names; `desc` points into them, so the image uploads, traces on the oracle and saves like one."""
+
+    def __init__(self, boxtree_size, brick_dim, arrays):
+        self.desc = N.TreeDesc()
+        self.desc.boxtree_size, self.desc.brick_dim = boxtree_size, brick_dim
+        for name, dt in TREE_ARRAYS:
+            a = np.ascontiguousarray(arrays[name], dt)
+            setattr(self, name, a)
+            setattr(self.desc, name, a.ctypes.data if a.size else None)
+        self.node_mips = np.zeros(0, np.uint32)
+        self.desc.node_count = self.node_type.size
+        self.desc.brick_count = self.voxels.size // brick_dim ** 3
+        self.desc.solid_count = self.solid_values.size
+        self.desc.color_count = self.color_palette.size
+        self.desc.data_count = self.data_palette.size
+
+    @property
+    def boxtree_size(self):
+        return self.desc.boxtree_size
+
+    @property
+    def brick_dim(self):
+        return self.desc.brick_dim
+
+    def counts(self):
+        d = self.desc
+        return dict(boxtree_size=d.boxtree_size, brick_dim=d.brick_dim, node_count=d.node_count,
+                    brick_count=d.brick_count, solid_count=d.solid_count, color_count=d.color_count,
+                    data_count=d.data_count)
+
+
 class FlatTree:
     """Flattened tree (vhx_tree_desc) owned by libvhx; arrays are zero-copy numpy views."""
 
@@ -347,6 +398,23 @@ class FlatTree:
         return FlatTree(h.value)
 
     @staticmethod
+    def from_dense(grid, size, brick_dim, threads=0):
+        """Bulk-builds the canonical tree of a dense grid (vhx_dense_build): `grid` is a uint32 numpy array of shape
+        (gz, gy, gx) of packed albedos r | g<<8 | b<<16 | a<<24 (alpha 0 = no voxel) sitting at the tree's origin. The
+        image equals inserting every voxel (x outer, y, z inner) into BoxTree(size, brick_dim) and flattening."""
+        d, keep = _dense_desc(grid, size, brick_dim)
+        h = ctypes.c_void_p()
+        _tree_check(N.lib().vhx_dense_build(ctypes.byref(d), threads, ctypes.byref(h)),
+                    f"dense grid {keep.shape[::-1]} size {size} brick_dim {brick_dim}")
+        return FlatTree(h.value)
+
+    def counts(self):
+        d = self.desc
+        return dict(boxtree_size=d.boxtree_size, brick_dim=d.brick_dim, node_count=d.node_count,
+                    brick_count=d.brick_count, solid_count=d.solid_count, color_count=d.color_count,
+                    data_count=d.data_count)
+
+    @staticmethod
     def build_scene_lod(scene, size, brick_dim, max_depth, seed=0x5EED, threads=0):
         """build_scene with the default MIP maps switched on and flattened like BoxTree.flatten_lod(max_depth): the
         image the insert loop + switch_albedo_mip_maps(True) + flatten_lod would give, without the insert loop."""
@@ -386,6 +454,16 @@ class BoxTree:
         h = ctypes.c_void_p()
         _tree_check(N.lib().vhx_scene_build_tree(scene, size, brick_dim, seed, threads, ctypes.byref(h)),
                     f"scene {scene} size {size} brick_dim {brick_dim}")
+        return cls._from_handle(h)
+
+    @classmethod
+    def from_dense(cls, grid, size, brick_dim, threads=0):
+        """The tree that inserting every voxel of a dense grid (FlatTree.from_dense) builds, from the bulk builder's
+        image (vhx_dense_build_tree); occlusion bits and MIP maps are not restored, as for from_scene."""
+        d, keep = _dense_desc(grid, size, brick_dim)
+        h = ctypes.c_void_p()
+        _tree_check(N.lib().vhx_dense_build_tree(ctypes.byref(d), threads, ctypes.byref(h)),
+                    f"dense grid {keep.shape[::-1]} size {size} brick_dim {brick_dim}")
         return cls._from_handle(h)
 
     @classmethod

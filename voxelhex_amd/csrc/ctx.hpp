@@ -123,6 +123,13 @@ struct vhx_ctx {
     DevBuf shadow_args;
     DevBuf upd;
     hipStream_t upd_stream = nullptr;  // the stream of the last scatter (reads upd)
+    // vhx_build_tree_dense (vhx_build.hip): scratch kept across builds and reset by each one -- the occupancy words of
+    // every possible node per level (the leaves' are their brick masks), their breadth-first ranks and first brick
+    // indices, the scans' block sums, the colour table with the palette ranked from it, the counters read back, and the
+    // device copy of a host grid
+    struct BuildScratch {
+        DevBuf occ, rank, first, part, table, ctl, grid;
+    } build;
     // depth-prepass mode (vhx_set_depth_prepass; opt-in, not the reference path)
     bool prepass = false, in_prepass = false;
     // fused hard shadows (vhx_set_shadow_light): each hit's shadow ray traced in the lane that finished its primary ray

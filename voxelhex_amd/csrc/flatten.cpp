@@ -10,7 +10,8 @@
 // to false before any node is touched), leaf nodes are exactly the nodes of edge 4*brick_dim, every brick that
 // received a voxel is Parted, and occupied_bits has a bit per non-empty child (post_process_node_insert,
 // insert.rs:428-449). vhx_scene_build writes that canonical image directly; tests check it buffer-equal against
-// vhx_scene_insert + vhx_boxtree_flatten.
+// vhx_scene_insert + vhx_boxtree_flatten. The image is a pure function of the voxels, so the same builder takes a caller's
+// dense grid (vhx_dense_build); vhx_build_tree_dense (vhx_build.hip) writes the same image on the GPU.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -316,40 +317,95 @@ static BoxTree *tree_of_flat(const vhx_flat &f) {
 }
 
 // ---------------------------------------------------------------------------------------------- bulk builder
-static int build_scene(uint32_t scene_id, uint32_t S, uint32_t bd, uint64_t seed, int threads, vhx_flat **out) {
-    BoxTree *probe = nullptr;
-    int rc = BoxTree::create(S, bd, &probe);  // same validity rules as BoxTree::new
-    if (rc != 0) return rc;
-    delete probe;
-    Scene sc{scene_id, S, seed, S, {}};
-    sc.prepare();
+// The voxel source of the bulk builder: a procedural scene, or a caller's dense grid (vhx_dense_desc). voxel() returns
+// the packed albedo, 0 = no voxel, and is defined for every position of the tree; voxels are only set inside
+// [0, ex) x [0, ey) x [0, ez).
+struct SceneSource {
+    const Scene &sc;
+    uint32_t ex, ey, ez;
+    explicit SceneSource(const Scene &s) : sc(s), ex(s.extent), ey(s.extent), ez(s.extent) {}
+    inline uint32_t voxel(uint32_t x, uint32_t y, uint32_t z) const { return sc.voxel(x, y, z); }
+};
+struct DenseSource {
+    const uint32_t *albedo;
+    uint32_t ex, ey, ez;
+    inline uint32_t voxel(uint32_t x, uint32_t y, uint32_t z) const {
+        if (x >= ex || y >= ey || z >= ez) return 0;
+        const uint32_t c = albedo[((uint64_t)z * ey + y) * ex + x];
+        return (c >> 24) ? c : 0;  // alpha 0: BoxTreeEntry::is_none of a Visual entry (boxtree.cpp entry_is_none)
+    }
+};
+
+// Palette in first-appearance order of the reference insert loop (x outer, y, z inner), slab by slab: the order a
+// procedural scene is evaluated in.
+static void palette_by_slabs(const SceneSource &src, int threads, std::vector<uint32_t> &palette) {
+    std::vector<std::vector<uint32_t>> slab_colors(src.ex);
+    parallel_for(src.ex, threads, [&](int64_t x) {
+        std::unordered_set<uint32_t> seen;
+        uint32_t last = 0;
+        for (uint32_t y = 0; y < src.ey; ++y)
+            for (uint32_t z = 0; z < src.ez; ++z) {
+                uint32_t c = src.voxel((uint32_t)x, y, z);
+                if (c == 0 || c == last) continue;
+                last = c;
+                if (seen.insert(c).second) slab_colors[x].push_back(c);
+            }
+    });
+    std::unordered_set<uint32_t> seen;
+    for (auto &sl : slab_colors)
+        for (uint32_t c : sl)
+            if (seen.insert(c).second) palette.push_back(c);
+}
+
+// The same palette for a dense grid, read in memory order (x runs fastest there, and the insert loop's z-inner walk
+// would touch a cache line per voxel): every colour's smallest insert-order index (x*gy + y)*gz + z, z plane by z plane,
+// then the colours sorted by it. A voxel whose left neighbour has its colour is skipped (the neighbour's index is smaller).
+static int palette_by_first_index(const DenseSource &src, int threads, std::vector<uint32_t> &palette) {
+    std::vector<std::unordered_map<uint32_t, uint64_t>> plane(src.ez);
+    parallel_for(src.ez, threads, [&](int64_t z) {
+        auto &first = plane[z];
+        for (uint32_t y = 0; y < src.ey; ++y) {
+            uint32_t last = 0;
+            for (uint32_t x = 0; x < src.ex; ++x) {
+                const uint32_t c = src.voxel(x, y, (uint32_t)z);
+                if (c == last) continue;
+                last = c;
+                if (c == 0) continue;
+                const uint64_t idx = ((uint64_t)x * src.ey + y) * src.ez + (uint64_t)z;
+                auto it = first.emplace(c, idx);
+                if (!it.second && idx < it.first->second) it.first->second = idx;
+            }
+        }
+    });
+    std::unordered_map<uint32_t, uint64_t> first;
+    for (auto &pl : plane) {
+        for (auto &kv : pl) {
+            auto it = first.emplace(kv.first, kv.second);
+            if (!it.second && kv.second < it.first->second) it.first->second = kv.second;
+        }
+        pl.clear();
+        if (first.size() > 0xFFFFu) return VHX_E_CAPACITY;  // 16-bit palette index, 0xFFFF = none
+    }
+    std::vector<std::pair<uint64_t, uint32_t>> order;
+    order.reserve(first.size());
+    for (auto &kv : first) order.emplace_back(kv.second, kv.first);
+    std::sort(order.begin(), order.end());
+    for (auto &o : order) palette.push_back(o.second);
+    return VHX_OK;
+}
+
+// Writes the canonical image of `src` into *f, whose size, brick_dim and colour palette are set.
+template <class Source>
+static int build_image(const Source &sc, int threads, vhx_flat *f) {
+    const uint32_t S = f->size, bd = f->brick_dim;
     const uint32_t L = 4 * bd;         // leaf node edge
     const uint32_t nl = S / L;         // leaf nodes per axis = 4^D
     uint32_t D = 0;
     while ((1u << (2 * D)) < nl) ++D;  // nl == 4^D
     const uint64_t nleaf = 1ull << (6 * D);
 
-    // 1) palette in first-appearance order of the reference insert loop (x outer, y, z inner)
-    std::vector<std::vector<uint32_t>> slab_colors(sc.extent);
-    parallel_for(sc.extent, threads, [&](int64_t x) {
-        std::unordered_set<uint32_t> seen;
-        uint32_t last = 0;
-        for (uint32_t y = 0; y < sc.extent; ++y)
-            for (uint32_t z = 0; z < sc.extent; ++z) {
-                uint32_t c = sc.voxel((uint32_t)x, y, z);
-                if (c == 0 || c == last) continue;
-                last = c;
-                if (seen.insert(c).second) slab_colors[x].push_back(c);
-            }
-    });
-    auto *f = new vhx_flat();
-    f->size = S;
-    f->brick_dim = bd;
     std::unordered_map<uint32_t, uint32_t> color_index;
-    for (auto &sl : slab_colors)
-        for (uint32_t c : sl)
-            if (color_index.emplace(c, (uint32_t)f->color_palette.size()).second) f->color_palette.push_back(c);
-    slab_colors.clear();
+    for (uint32_t c : f->color_palette) color_index.emplace(c, (uint32_t)color_index.size());
 
     // leaf path code -> leaf coordinates (digit i of the code = sectant taken at depth i)
     auto leaf_coord = [&](uint64_t code, uint32_t &lx, uint32_t &ly, uint32_t &lz) {
@@ -367,7 +423,7 @@ static int build_scene(uint32_t scene_id, uint32_t S, uint32_t bd, uint64_t seed
         uint32_t lx, ly, lz;
         leaf_coord((uint64_t)code, lx, ly, lz);
         uint32_t x0 = lx * L, y0 = ly * L, z0 = lz * L;
-        if (x0 >= sc.extent || y0 >= sc.extent || z0 >= sc.extent) return;
+        if (x0 >= sc.ex || y0 >= sc.ey || z0 >= sc.ez) return;
         uint64_t m = 0;
         for (uint32_t s = 0; s < 64; ++s) {
             uint32_t bx = x0 + (s & 3u) * bd, by = y0 + ((s >> 2) & 3u) * bd, bz = z0 + (s >> 4) * bd;
@@ -414,18 +470,12 @@ static int build_scene(uint32_t scene_id, uint32_t S, uint32_t bd, uint64_t seed
     std::vector<uint64_t> leaf_first(nleaf + 1, 0);
     for (uint64_t c = 0; c < nleaf; ++c) leaf_first[c + 1] = leaf_first[c] + (uint64_t)__builtin_popcountll(leaf_mask[c]);
     const uint64_t nbricks = leaf_first[nleaf];
-    if (nbricks >= 0x80000000ull) {
-        delete f;
-        return VHX_E_CAPACITY;
-    }
+    if (nbricks >= 0x80000000ull) return VHX_E_CAPACITY;
     const size_t n3 = (size_t)bd * bd * bd;
     f->brick_count = (uint32_t)nbricks;
     f->voxel_count = nbricks * n3;
     f->voxels.reset(new (std::nothrow) uint32_t[std::max<uint64_t>(f->voxel_count, 1)]);
-    if (!f->voxels) {
-        delete f;
-        return VHX_E_CAPACITY;
-    }
+    if (!f->voxels) return VHX_E_CAPACITY;
     uint32_t *vox = f->voxels.get();
     parallel_for((int64_t)nleaf, threads, [&](int64_t code) {
         uint64_t m = leaf_mask[code];
@@ -457,8 +507,47 @@ static int build_scene(uint32_t scene_id, uint32_t S, uint32_t bd, uint64_t seed
             ++b;
         }
     });
-    *out = f;
-    return 0;
+    return VHX_OK;
+}
+
+static int check_sizes(uint32_t S, uint32_t bd) {
+    BoxTree *probe = nullptr;
+    int rc = BoxTree::create(S, bd, &probe);  // same validity rules as BoxTree::new
+    if (rc != 0) return rc;
+    delete probe;
+    return VHX_OK;
+}
+
+static int build_scene(uint32_t scene_id, uint32_t S, uint32_t bd, uint64_t seed, int threads, vhx_flat **out) {
+    int rc = check_sizes(S, bd);
+    if (rc != 0) return rc;
+    Scene sc{scene_id, S, seed, S, {}};
+    sc.prepare();
+    SceneSource src(sc);
+    std::unique_ptr<vhx_flat> f(new vhx_flat());
+    f->size = S;
+    f->brick_dim = bd;
+    palette_by_slabs(src, threads, f->color_palette);
+    if ((rc = build_image(src, threads, f.get())) != 0) return rc;
+    *out = f.release();
+    return VHX_OK;
+}
+
+static int build_dense(const vhx_dense_desc *g, int threads, vhx_flat **out) {
+    if (!g) return VHX_E_INVALID_ARG;
+    int rc = check_sizes(g->boxtree_size, g->brick_dim);
+    if (rc != 0) return rc;
+    const uint32_t S = g->boxtree_size;
+    if (!g->albedo || g->gx == 0 || g->gy == 0 || g->gz == 0 || g->gx > S || g->gy > S || g->gz > S)
+        return VHX_E_INVALID_ARG;
+    DenseSource src{g->albedo, g->gx, g->gy, g->gz};
+    std::unique_ptr<vhx_flat> f(new vhx_flat());
+    f->size = S;
+    f->brick_dim = g->brick_dim;
+    if ((rc = palette_by_first_index(src, threads, f->color_palette)) != 0) return rc;
+    if ((rc = build_image(src, threads, f.get())) != 0) return rc;
+    *out = f.release();
+    return VHX_OK;
 }
 
 // ---------------------------------------------------------------------------------------------- C ABI
@@ -647,6 +736,31 @@ int vhx_scene_build_tree(uint32_t scene, uint32_t size, uint32_t brick_dim, uint
     try {
         vhx_flat *full = nullptr;
         int rc = build_scene(scene, size, brick_dim, seed, threads, &full);
+        if (rc != VHX_OK) return rc;
+        std::unique_ptr<vhx_flat> owned(full);
+        BoxTree *t = tree_of_flat(*full);
+        if (!t) return VHX_E_STATE;
+        *out = new vhx_boxtree{t};
+        return VHX_OK;
+    } catch (const std::bad_alloc &) {
+        return VHX_E_CAPACITY;
+    }
+}
+int vhx_dense_build(const vhx_dense_desc *grid, int threads, vhx_flat **out) {
+    if (!out) return VHX_E_INVALID_ARG;
+    *out = nullptr;
+    try {
+        return build_dense(grid, threads, out);
+    } catch (const std::bad_alloc &) {
+        return VHX_E_CAPACITY;
+    }
+}
+int vhx_dense_build_tree(const vhx_dense_desc *grid, int threads, vhx_boxtree **out) {
+    if (!out) return VHX_E_INVALID_ARG;
+    *out = nullptr;
+    try {
+        vhx_flat *full = nullptr;
+        int rc = build_dense(grid, threads, &full);
         if (rc != VHX_OK) return rc;
         std::unique_ptr<vhx_flat> owned(full);
         BoxTree *t = tree_of_flat(*full);

@@ -1,0 +1,594 @@
+// vhx_build_tree_dense: the canonical flattened tree of a dense voxel grid, built on the GPU into the context's tree
+// buffers (the image vhx_dense_build of flatten.cpp writes on the host, bit for bit), and the read-back of a device tree
+// (vhx_tree_counts, vhx_read_range).
+//
+// The image is a pure function of the grid (flatten.cpp, top): leaves are the nodes of edge 4*brick_dim, a node exists
+// where a voxel lies below it, nodes are numbered breadth-first level by level in path-code order, bricks in (leaf,
+// sectant) order, colours by their first appearance in the insert loop (x outer, y, z inner). With
+// boxtree_size = brick_dim * 4^(D+1) the tree has levels 0..D and 64^lv possible nodes at level lv, addressed by their
+// path code (6 bits per level, the root's sectant first).
+//
+//   pass A   k_dense_scan      reads the grid once in memory order: ORs every non-empty brick's bit into its leaf's
+//                              mask (occ level D) and records every colour's smallest insert-order index
+//                              (x*gy + y)*gz + z in an open-addressing table; both deduplicated inside the wave first
+//   levels   k_reduce_level    occ[lv][p] = which of p's 64 children have a non-zero word (one wave per parent, ballot)
+//   scans    k_scan_*          per level: exclusive scan of "node present" = the node's rank inside its level; for the
+//                              leaves also of popcount(mask) = the leaf's first brick index
+//   palette  k_pal_*           the table's entries compacted and ranked by first index: the palette, and each table
+//                              entry's palette index
+//   -- one readback of the counters; nothing of the context's tree has been touched so far --
+//   fill     k_emit_nodes      node types, occupancy and children, level by level, into the tree's raw buffers
+//            k_emit_bricks     the cells of every present brick gathered from the grid and translated through the table
+//
+// Every atomic is an OR, a minimum, a constant store or the claim of a table slot, and every order that reaches a
+// buffer comes from a scan or from the first indices, so the buffers do not depend on scheduling. Grid offsets are
+// 64-bit; nothing outside [0,gx) x [0,gy) x [0,gz) is read.
+#include <algorithm>
+
+#include "../../include/vhx_boxtree.h"
+#include "ctx.hpp"
+
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr uint32_t TAB_SLOTS = 1u << 18;  // four times the colours a palette holds: short probe chains
+constexpr uint32_t TAB_MASK = TAB_SLOTS - 1;
+constexpr uint32_t MAX_COLORS = 0xFFFFu;  // the palette index has 16 bits, 0xFFFF = none
+constexpr uint32_t PAL_CAP = 1u << 16;
+constexpr uint32_t MAX_LEVELS = 8;
+constexpr uint64_t MAX_LEAVES = 1ull << 28;  // possible leaf nodes (scratch words per array)
+constexpr uint32_t SCAN_ITEMS = 4, SCAN_TILE = 256 * SCAN_ITEMS;
+constexpr uint32_t SCAN_ROWS = 4;  // grid rows per thread of pass A
+
+// the counters of a build, read back once
+struct BuildCtl {
+    u64 level_total[MAX_LEVELS];  // nodes per level
+    u64 brick_total;
+    uint32_t ncolors;   // table slots claimed
+    uint32_t overflow;  // more than MAX_COLORS colours
+    uint32_t ncompact;
+    uint32_t pad;
+};
+
+// vhx_ctx::build.table
+struct ColorTable {
+    u64 *vals;        // [TAB_SLOTS] smallest insert-order index of the slot's colour; after k_pal_rank its palette index
+    u64 *cidx;        // [PAL_CAP]   compacted: first index
+    uint32_t *keys;   // [TAB_SLOTS] colour, 0 = free (a voxel's colour has a non-zero alpha byte)
+    uint32_t *ckey;   // [PAL_CAP]   compacted: colour
+    uint32_t *cslot;  // [PAL_CAP]   compacted: table slot
+    uint32_t *pal;    // [PAL_CAP]   the palette
+};
+constexpr uint64_t TAB_VALS_BYTES = (uint64_t)TAB_SLOTS * 8, TAB_CIDX_BYTES = (uint64_t)PAL_CAP * 8,
+                   TAB_KEYS_BYTES = (uint64_t)TAB_SLOTS * 4, TAB_BYTES = TAB_VALS_BYTES + TAB_CIDX_BYTES +
+                                                                        TAB_KEYS_BYTES + 3ull * PAL_CAP * 4;
+ColorTable table_of(void *base) {
+    ColorTable t;
+    uint8_t *p = (uint8_t *)base;
+    t.vals = (u64 *)p;
+    t.cidx = (u64 *)(p + TAB_VALS_BYTES);
+    t.keys = (uint32_t *)(p + TAB_VALS_BYTES + TAB_CIDX_BYTES);
+    t.ckey = t.keys + TAB_SLOTS;
+    t.cslot = t.ckey + PAL_CAP;
+    t.pal = t.cslot + PAL_CAP;
+    return t;
+}
+
+struct GridP {
+    const uint32_t *a;
+    uint32_t gx, gy, gz;
+    uint32_t bsh;  // log2(brick_dim)
+    uint32_t D;    // leaf level
+};
+
+__device__ inline uint32_t color_hash(uint32_t c) {
+    c *= 0x9E3779B1u;
+    c ^= c >> 15;
+    c *= 0x85EBCA77u;
+    c ^= c >> 13;
+    return c & TAB_MASK;
+}
+
+// path code of the leaf with coordinates (lx, ly, lz): digit i (from the top) = the sectant taken at depth i
+__device__ inline uint32_t leaf_code(uint32_t lx, uint32_t ly, uint32_t lz, uint32_t D) {
+    uint32_t code = 0;
+    for (uint32_t i = 0; i < D; ++i)
+        code |= (((lx >> (2 * i)) & 3u) | (((ly >> (2 * i)) & 3u) << 2) | (((lz >> (2 * i)) & 3u) << 4)) << (6 * i);
+    return code;
+}
+
+// Records colour c seen at insert-order index idx. The slot of a colour is claimed by compare-and-swap (whoever wins,
+// the slot then holds c); the count of claims detects a table that would hold more colours than a palette can, after
+// which inserts stop (the build fails) -- so the probe loop ends even when a grid holds millions of colours.
+__device__ inline void color_insert(const ColorTable t, BuildCtl *ctl, uint32_t c, u64 idx) {
+    uint32_t h = color_hash(c);
+    for (uint32_t probe = 0; probe < TAB_SLOTS; ++probe, h = (h + 1) & TAB_MASK) {
+        if ((probe & 63u) == 0 && __hip_atomic_load(&ctl->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+        uint32_t k = t.keys[h];  // a stale 0 is settled by the compare-and-swap; a colour never leaves its slot
+        if (k == 0) {
+            k = atomicCAS(&t.keys[h], 0u, c);
+            if (k == 0) {
+                if (atomicAdd(&ctl->ncolors, 1u) >= MAX_COLORS) atomicOr(&ctl->overflow, 1u);
+                k = c;
+            }
+        }
+        if (k == c) {
+            // the index only ever shrinks, so a larger one needs no atomic (a stale read only costs the atomic)
+            if (t.vals[h] > idx) atomicMin(&t.vals[h], idx);
+            return;
+        }
+    }
+}
+
+// palette index of colour c (after k_pal_rank); 0xFFFF where the table does not hold it
+__device__ inline uint32_t color_lookup(const ColorTable t, uint32_t c) {
+    uint32_t h = color_hash(c);
+    for (uint32_t probe = 0; probe < TAB_SLOTS; ++probe, h = (h + 1) & TAB_MASK) {
+        const uint32_t k = t.keys[h];
+        if (k == c) return (uint32_t)t.vals[h] & 0xFFFFu;
+        if (k == 0) break;
+    }
+    return 0xFFFFu;
+}
+
+// Pass A. A block covers `tpr` = 2^xsh vector columns of 256 / tpr row groups; a thread reads VEC voxels consecutive in
+// x (VEC = 4: one 16-byte load; gx is then a multiple of 4 and the grid 16-byte aligned) of SCAN_ROWS = 4 rows
+// consecutive in y, starting at a multiple of 4: a leaf's edge is a multiple of 4, so all of a thread's voxels share a
+// leaf. The loops are the same for every thread of a block, so the wave operations below always run with all 64 lanes.
+template <int VEC>
+__global__ __launch_bounds__(256) void k_dense_scan(GridP g, uint32_t xsh, u64 *leaf_mask, ColorTable t, BuildCtl *ctl) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t tpr = 1u << xsh, rpb = 256u >> xsh;
+    const uint32_t gxv = (g.gx + VEC - 1) / VEC;
+    const uint32_t xv = blockIdx.x * tpr + (tid & (tpr - 1u));
+    const uint32_t x0 = xv * VEC;
+    const uint32_t sub = tid >> xsh;  // the thread's row group inside the block
+    const uint32_t ytiles = (g.gy + rpb * SCAN_ROWS - 1) / (rpb * SCAN_ROWS);
+    const uint32_t lsh = g.bsh + 2;
+    const bool row_start = lane == 0 || (tid & (tpr - 1u)) == 0;  // the previous lane is not this thread's left neighbour
+    for (uint32_t z = blockIdx.z; z < g.gz; z += gridDim.z)
+        for (uint32_t yt = blockIdx.y; yt < ytiles; yt += gridDim.y) {
+            const uint32_t yb = (yt * rpb + sub) * SCAN_ROWS;
+            uint32_t v[SCAN_ROWS][VEC];
+#pragma unroll
+            for (uint32_t j = 0; j < SCAN_ROWS; ++j) {
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) v[j][i] = 0;
+                if (xv < gxv && yb + j < g.gy) {
+                    const uint64_t at = ((uint64_t)z * g.gy + (yb + j)) * g.gx + (uint64_t)xv * VEC;
+                    if constexpr (VEC == 4) {
+                        const uint4 q = *reinterpret_cast<const uint4 *>(g.a + at);
+                        v[j][0] = q.x;
+                        v[j][1] = q.y;
+                        v[j][2] = q.z;
+                        v[j][3] = q.w;
+                    } else {
+                        v[j][0] = g.a[at];
+                    }
+                }
+            }
+            u64 m = 0;
+#pragma unroll
+            for (uint32_t j = 0; j < SCAN_ROWS; ++j) {
+                const uint32_t y = yb + j;
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) {
+                    if ((v[j][i] >> 24) == 0) v[j][i] = 0;  // alpha 0: no voxel
+                    if (v[j][i]) {
+                        const uint32_t s = (((x0 + i) >> g.bsh) & 3u) | (((y >> g.bsh) & 3u) << 2) | (((z >> g.bsh) & 3u) << 4);
+                        m |= 1ull << s;
+                    }
+                }
+                // Colours. A voxel is skipped when a voxel of its colour further left in its row is in this wave: that
+                // one's insert-order index is smaller. First the left neighbour and the thread's own voxels; then, per
+                // colour, the lowest lane of a row group records it for the group (x grows with the lane there).
+                uint32_t left = __shfl_up(v[j][VEC - 1], 1);
+                if (row_start) left = 0;
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) {
+                    const uint32_t c = v[j][i];
+                    bool cand = c != 0 && c != left;
+#pragma unroll
+                    for (int e = 0; e + 1 < i; ++e) cand = cand && v[j][e] != c;
+                    left = c;
+                    u64 pending = __ballot(cand);
+                    while (pending) {  // the same in every lane
+                        const uint32_t leader = (uint32_t)__ffsll((long long)pending) - 1u;
+                        const uint32_t lc = __shfl(c, leader), lsub = __shfl(sub, leader);
+                        const bool mine = cand && c == lc && sub == lsub;
+                        if (lane == leader) color_insert(t, ctl, c, ((u64)(x0 + i) * g.gy + y) * g.gz + z);
+                        pending &= ~__ballot(mine);
+                    }
+                }
+            }
+            // brick bits: OR over each run of lanes in the same leaf, one atomic per run, and none where the mask already
+            // holds the bits (a stale read only costs the atomic)
+            const uint32_t key = m ? leaf_code(x0 >> lsh, yb >> lsh, z >> lsh, g.D) : 0xFFFFFFFFu;
+#pragma unroll
+            for (uint32_t k = 1; k < 64; k <<= 1) {
+                const uint32_t ok = __shfl_down(key, k);
+                const u64 om = __shfl_down(m, k);
+                if (lane + k < 64 && ok == key) m |= om;
+            }
+            const uint32_t pk = __shfl_up(key, 1);
+            if (m && (lane == 0 || pk != key) && (leaf_mask[key] & m) != m) atomicOr(&leaf_mask[key], m);
+        }
+}
+
+// occ[lv][p]: bit s = child s of p (occ[lv + 1][64 p + s]) is not empty. One wave per parent.
+__global__ __launch_bounds__(256) void k_reduce_level(const u64 *child, u64 *parent, uint64_t nparent) {
+    const uint64_t p = ((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
+    const uint32_t lane = threadIdx.x & 63u;
+    if (p >= nparent) return;  // the whole wave
+    const u64 b = __ballot(child[p * 64 + lane] != 0);
+    if (lane == 0) parent[p] = b;
+}
+
+// ---- scans over the occupancy words of a level: MODE 0 "the node exists" (the root always does), MODE 1 its bricks
+template <int MODE>
+__device__ inline uint32_t scan_value(u64 w, bool root) {
+    return MODE == 0 ? (uint32_t)(w != 0 || root) : (uint32_t)__popcll(w);
+}
+
+// inclusive scan over the block's 256 threads (lds: 4 words)
+__device__ inline u64 block_scan(u64 v, u64 *lds) {
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+#pragma unroll
+    for (uint32_t k = 1; k < 64; k <<= 1) {
+        const u64 o = __shfl_up(v, k);
+        if (lane >= k) v += o;
+    }
+    if (lane == 63) lds[w] = v;
+    __syncthreads();
+    u64 add = 0;
+    for (uint32_t i = 0; i < w; ++i) add += lds[i];
+    __syncthreads();
+    return v + add;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_scan_sums(const u64 *occ, uint64_t n, int root, u64 *part) {
+    __shared__ u64 lds[4];
+    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
+    u64 s = 0;
+    for (uint32_t i = 0; i < SCAN_ITEMS; ++i)
+        if (base + i < n) s += scan_value<MODE>(occ[base + i], root != 0);
+    s = block_scan(s, lds);
+    if (threadIdx.x == 255) part[blockIdx.x] = s;
+}
+
+// exclusive scan of the nb block sums in place (one block), the total to *total
+__global__ __launch_bounds__(256) void k_scan_top(u64 *part, uint64_t nb, u64 *total) {
+    __shared__ u64 lds[4];
+    __shared__ u64 carry;
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    for (uint64_t c0 = 0; c0 < nb; c0 += 256) {
+        const uint64_t i = c0 + threadIdx.x;
+        const u64 v = i < nb ? part[i] : 0;
+        const u64 incl = block_scan(v, lds);
+        if (i < nb) part[i] = carry + incl - v;
+        __syncthreads();
+        if (threadIdx.x == 255) carry += incl;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_scan_apply(const u64 *occ, uint64_t n, int root, const u64 *part, u64 *out) {
+    __shared__ u64 lds[4];
+    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
+    uint32_t v[SCAN_ITEMS];
+    u64 s = 0;
+    for (uint32_t i = 0; i < SCAN_ITEMS; ++i) {
+        v[i] = base + i < n ? scan_value<MODE>(occ[base + i], root != 0) : 0u;
+        s += v[i];
+    }
+    u64 run = part[blockIdx.x] + block_scan(s, lds) - s;
+    for (uint32_t i = 0; i < SCAN_ITEMS; ++i) {
+        if (base + i < n) out[base + i] = run;
+        run += v[i];
+    }
+}
+
+// ---- palette
+__global__ __launch_bounds__(256) void k_pal_compact(ColorTable t, BuildCtl *ctl) {
+    const uint32_t h = blockIdx.x * 256 + threadIdx.x;
+    if (h >= TAB_SLOTS) return;
+    const uint32_t k = t.keys[h];
+    if (k == 0) return;
+    const uint32_t pos = atomicAdd(&ctl->ncompact, 1u);  // any order: the ranks below come from the first indices
+    if (pos >= PAL_CAP) return;
+    t.ckey[pos] = k;
+    t.cidx[pos] = t.vals[h];
+    t.cslot[pos] = h;
+}
+
+// palette position of a colour = how many colours appear before it (first indices are distinct)
+__global__ __launch_bounds__(256) void k_pal_rank(ColorTable t, const BuildCtl *ctl) {
+    __shared__ u64 tile[256];
+    const uint32_t n = min(ctl->ncompact, PAL_CAP);
+    if (blockIdx.x * 256u >= n) return;  // the whole block
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    const u64 mine = i < n ? t.cidx[i] : 0;
+    uint32_t rank = 0;
+    for (uint32_t j0 = 0; j0 < n; j0 += 256) {
+        tile[threadIdx.x] = j0 + threadIdx.x < n ? t.cidx[j0 + threadIdx.x] : ~0ull;
+        __syncthreads();
+        const uint32_t m = min(256u, n - j0);
+        for (uint32_t j = 0; j < m; ++j) rank += tile[j] < mine;
+        __syncthreads();
+    }
+    if (i < n) {
+        t.pal[rank] = t.ckey[i];
+        t.vals[t.cslot[i]] = rank;
+    }
+}
+
+// ---- emission into the tree's raw buffers
+// One thread per (possible node c of level lv, sectant s). Children: the child's breadth-first index (lv < D) or the
+// brick index of the leaf's sectant (lv == D).
+__global__ __launch_bounds__(256) void k_emit_nodes(uint32_t lv, uint32_t D, uint64_t n, const u64 *occ, const u64 *rank,
+                                                    const u64 *rank_child, const u64 *first, uint32_t base,
+                                                    uint32_t base_child, uint32_t *node_type, u64 *node_ocbits,
+                                                    uint32_t *node_children) {
+    const uint64_t gid = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint64_t c = gid >> 6;
+    const uint32_t s = (uint32_t)gid & 63u;
+    if (c >= n) return;
+    const u64 w = occ[c];
+    if (w == 0 && lv != 0) return;  // no such node
+    const uint64_t ni = (uint64_t)base + rank[c];
+    if (s == 0) {
+        node_type[ni] = w ? (lv < D ? VHX_NODE_INTERNAL : VHX_NODE_LEAF) : VHX_NODE_NOTHING;
+        node_ocbits[ni] = w;
+    }
+    uint32_t child = VHX_EMPTY;
+    if ((w >> s) & 1ull)
+        child = lv < D ? base_child + (uint32_t)rank_child[c * 64 + s]
+                       : (uint32_t)(first[c] + (u64)__popcll(w & ((1ull << s) - 1ull)));
+    node_children[ni * 64 + s] = child;
+}
+
+// One block per leaf at a time: the cells of its bricks are one contiguous run of the voxel buffer, written in order.
+__global__ __launch_bounds__(256) void k_emit_bricks(GridP g, const u64 *leaf_mask, const u64 *first, uint64_t nleaf,
+                                                     ColorTable t, uint32_t *voxels) {
+    __shared__ uint8_t sect[64];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t bd = 1u << g.bsh, n3sh = 3 * g.bsh, lsh = g.bsh + 2;
+    uint32_t last_c = 0, last_v = VHX_EMPTY;
+    for (uint64_t code = blockIdx.x; code < nleaf; code += gridDim.x) {
+        const u64 m = leaf_mask[code];
+        if (m == 0) continue;  // the whole block
+        if (tid < 64 && ((m >> tid) & 1ull)) sect[__popcll(m & ((1ull << tid) - 1ull))] = (uint8_t)tid;
+        __syncthreads();
+        uint32_t lx = 0, ly = 0, lz = 0;
+        for (uint32_t i = 0; i < g.D; ++i) {
+            const uint32_t d = (uint32_t)(code >> (6 * i)) & 63u;
+            lx |= (d & 3u) << (2 * i);
+            ly |= ((d >> 2) & 3u) << (2 * i);
+            lz |= (d >> 4) << (2 * i);
+        }
+        const uint32_t total = (uint32_t)__popcll(m) << n3sh;
+        uint32_t *dst = voxels + (first[code] << n3sh);
+        for (uint32_t j = tid; j < total; j += 256) {
+            const uint32_t s = sect[j >> n3sh], i = j & ((1u << n3sh) - 1u);
+            const uint32_t x = (lx << lsh) + ((s & 3u) << g.bsh) + (i & (bd - 1u));
+            const uint32_t y = (ly << lsh) + (((s >> 2) & 3u) << g.bsh) + ((i >> g.bsh) & (bd - 1u));
+            const uint32_t z = (lz << lsh) + ((s >> 4) << g.bsh) + (i >> (2 * g.bsh));
+            uint32_t c = 0;
+            if (x < g.gx && y < g.gy && z < g.gz) c = g.a[((uint64_t)z * g.gy + y) * g.gx + x];
+            uint32_t v = VHX_EMPTY;
+            if (c >> 24) {
+                if (c != last_c) {
+                    last_c = c;
+                    last_v = color_lookup(t, c) | 0xFFFF0000u;  // pix_visual: colour index, no data
+                }
+                v = last_v;
+            }
+            dst[j] = v;
+        }
+        __syncthreads();  // sect is rewritten for the next leaf
+    }
+}
+
+struct FillArg {
+    vhx_ctx *c;
+    GridP g;
+    uint32_t levels;
+    uint64_t level_off[MAX_LEVELS];
+    uint32_t level_base[MAX_LEVELS];
+    uint32_t color_count;
+};
+
+inline unsigned blocks_for(uint64_t threads) { return (unsigned)((threads + 255) / 256); }
+
+// receive_tree's fill step: the emission kernels write straight into the tree's raw buffers
+int fill_from_scratch(void *arg, void *const dst[7], const uint64_t bytes[7]) {
+    const FillArg &a = *(const FillArg *)arg;
+    vhx_ctx *c = a.c;
+    const u64 *occ = (const u64 *)c->build.occ.ptr, *rank = (const u64 *)c->build.rank.ptr;
+    const u64 *first = (const u64 *)c->build.first.ptr;
+    const ColorTable t = table_of(c->build.table.ptr);
+    const uint32_t D = a.levels - 1;
+    for (uint32_t lv = 0; lv <= D; ++lv) {
+        const uint64_t n = 1ull << (6 * lv);
+        const uint64_t child_off = lv < D ? a.level_off[lv + 1] : 0;
+        k_emit_nodes<<<blocks_for(n * 64), 256, 0, c->stream>>>(
+            lv, D, n, occ + a.level_off[lv], rank + a.level_off[lv], rank + child_off, first, a.level_base[lv],
+            lv < D ? a.level_base[lv + 1] : 0u, (uint32_t *)dst[VHX_BUF_NODE_TYPE], (u64 *)dst[VHX_BUF_NODE_OCBITS],
+            (uint32_t *)dst[VHX_BUF_NODE_CHILDREN]);
+    }
+    VHX_HIP(c, hipGetLastError());
+    if (bytes[VHX_BUF_VOXELS]) {
+        const uint64_t nleaf = 1ull << (6 * D);
+        k_emit_bricks<<<(unsigned)std::min<uint64_t>(nleaf, (uint64_t)c->cus * 16), 256, 0, c->stream>>>(
+            a.g, occ + a.level_off[D], first, nleaf, t, (uint32_t *)dst[VHX_BUF_VOXELS]);
+        VHX_HIP(c, hipGetLastError());
+    }
+    if (bytes[VHX_BUF_COLOR_PALETTE])
+        VHX_HIP(c, hipMemcpyAsync(dst[VHX_BUF_COLOR_PALETTE], t.pal, (uint64_t)a.color_count * 4,
+                                  hipMemcpyDeviceToDevice, c->stream));
+    return VHX_OK;
+}
+
+template <int MODE>
+int scan_level(vhx_ctx *c, const u64 *occ, uint64_t n, bool root, u64 *out, u64 *total) {
+    u64 *part = (u64 *)c->build.part.ptr;
+    const uint64_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
+    k_scan_sums<MODE><<<(unsigned)nb, 256, 0, c->stream>>>(occ, n, root ? 1 : 0, part);
+    k_scan_top<<<1, 256, 0, c->stream>>>(part, nb, total);
+    k_scan_apply<MODE><<<(unsigned)nb, 256, 0, c->stream>>>(occ, n, root ? 1 : 0, part, out);
+    VHX_HIP(c, hipGetLastError());
+    return VHX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vhx_build_tree_dense(vhx_ctx *c, const vhx_dense_desc *grid, int on_device) {
+    if (!c || !grid) return fail(c, VHX_E_INVALID_ARG, "vhx_build_tree_dense: null argument");
+    if (c->shared) return fail(c, VHX_E_STATE, "vhx_build_tree_dense on a shared context: build through the owner");
+    {
+        vhx_boxtree *probe = nullptr;  // the validity rules of BoxTree::new
+        const int rc = vhx_boxtree_new(grid->boxtree_size, grid->brick_dim, &probe);
+        if (rc) return fail(c, rc, "vhx_build_tree_dense: invalid boxtree_size / brick_dim");
+        vhx_boxtree_free(probe);
+    }
+    const uint32_t S = grid->boxtree_size, bd = grid->brick_dim;
+    if (!grid->albedo || grid->gx == 0 || grid->gy == 0 || grid->gz == 0 || grid->gx > S || grid->gy > S || grid->gz > S)
+        return fail(c, VHX_E_INVALID_ARG, "vhx_build_tree_dense: null grid, or an extent of 0 or above boxtree_size");
+    if ((bd & (bd - 1)) != 0 || (S & (S - 1)) != 0 || S < 4 * bd)
+        return fail(c, VHX_E_INVALID_ARG, "vhx_build_tree_dense: sizes must be powers of two");
+    GridP g{};
+    g.gx = grid->gx;
+    g.gy = grid->gy;
+    g.gz = grid->gz;
+    while ((1u << g.bsh) < bd) ++g.bsh;
+    const uint32_t nl = S / (4 * bd);  // leaf nodes per axis = 4^D
+    while ((1u << (2 * g.D)) < nl) ++g.D;
+    if ((1u << (2 * g.D)) != nl)
+        return fail(c, VHX_E_INVALID_ARG, "vhx_build_tree_dense: boxtree_size is not brick_dim * 4^k");
+    const uint32_t D = g.D, levels = D + 1;
+    const uint64_t nleaf = 1ull << (6 * D);
+    if (levels > MAX_LEVELS || nleaf > MAX_LEAVES)
+        return fail(c, VHX_E_CAPACITY, "vhx_build_tree_dense: more than 2^28 possible leaf nodes");
+    FillArg fa{};
+    fa.c = c;
+    fa.levels = levels;
+    uint64_t words = 0;
+    for (uint32_t lv = 0; lv < levels; ++lv) {
+        fa.level_off[lv] = words;
+        words += 1ull << (6 * lv);
+    }
+
+    VHX_HIP(c, hipSetDevice(c->device));
+    VHX_STREAM(c);
+    // scratch: a buffer that grows is reallocated, which waits for the device (the previous build has completed: the
+    // call is synchronous)
+    int rc;
+    if ((rc = vhx::ensure(c, c->build.occ, words * 8))) return rc;
+    if ((rc = vhx::ensure(c, c->build.rank, words * 8))) return rc;
+    if ((rc = vhx::ensure(c, c->build.first, nleaf * 8))) return rc;
+    if ((rc = vhx::ensure(c, c->build.part, ((nleaf + SCAN_TILE - 1) / SCAN_TILE) * 8))) return rc;
+    if ((rc = vhx::ensure(c, c->build.table, TAB_BYTES))) return rc;
+    if ((rc = vhx::ensure(c, c->build.ctl, sizeof(BuildCtl)))) return rc;
+    const uint64_t voxels = (uint64_t)g.gx * g.gy * g.gz;
+    if (on_device) {
+        g.a = grid->albedo;
+    } else {
+        if ((rc = vhx::ensure(c, c->build.grid, voxels * 4))) return rc;
+        VHX_HIP(c, hipMemcpyAsync(c->build.grid.ptr, grid->albedo, voxels * 4, hipMemcpyHostToDevice, c->stream));
+        g.a = (const uint32_t *)c->build.grid.ptr;
+    }
+    fa.g = g;
+    u64 *occ = (u64 *)c->build.occ.ptr, *rank = (u64 *)c->build.rank.ptr, *first = (u64 *)c->build.first.ptr;
+    BuildCtl *ctl = (BuildCtl *)c->build.ctl.ptr;
+    const ColorTable t = table_of(c->build.table.ptr);
+    // full reset: leaf masks (the other levels are overwritten), counters, table keys free, first indices at maximum
+    VHX_HIP(c, hipMemsetAsync(occ, 0, words * 8, c->stream));
+    VHX_HIP(c, hipMemsetAsync(ctl, 0, sizeof(BuildCtl), c->stream));
+    VHX_HIP(c, hipMemsetAsync(t.keys, 0, TAB_KEYS_BYTES, c->stream));
+    VHX_HIP(c, hipMemsetAsync(t.vals, 0xFF, TAB_VALS_BYTES, c->stream));
+
+    // pass A
+    {
+        const bool vec = (g.gx % 4u) == 0 && ((uintptr_t)g.a % 16u) == 0;
+        const uint32_t gxv = vec ? g.gx / 4 : g.gx;
+        uint32_t xsh = 0;
+        while (xsh < 8 && (1u << xsh) < gxv) ++xsh;
+        const uint32_t tpr = 1u << xsh, rpb = 256u >> xsh;
+        const dim3 blocks((gxv + tpr - 1) / tpr, std::min<uint32_t>((g.gy + rpb * SCAN_ROWS - 1) / (rpb * SCAN_ROWS), 65535u),
+                          std::min<uint32_t>(g.gz, 65535u));
+        if (vec)
+            k_dense_scan<4><<<blocks, 256, 0, c->stream>>>(g, xsh, occ + fa.level_off[D], t, ctl);
+        else
+            k_dense_scan<1><<<blocks, 256, 0, c->stream>>>(g, xsh, occ + fa.level_off[D], t, ctl);
+        VHX_HIP(c, hipGetLastError());
+    }
+    // occupancy upwards, ranks per level, first brick of every leaf
+    for (uint32_t lv = D; lv-- > 0;) {
+        const uint64_t np = 1ull << (6 * lv);
+        k_reduce_level<<<blocks_for(np * 64), 256, 0, c->stream>>>(occ + fa.level_off[lv + 1], occ + fa.level_off[lv], np);
+    }
+    VHX_HIP(c, hipGetLastError());
+    for (uint32_t lv = 0; lv < levels; ++lv)
+        if ((rc = scan_level<0>(c, occ + fa.level_off[lv], 1ull << (6 * lv), lv == 0, rank + fa.level_off[lv],
+                                &ctl->level_total[lv])))
+            return rc;
+    if ((rc = scan_level<1>(c, occ + fa.level_off[D], nleaf, false, first, &ctl->brick_total))) return rc;
+    // palette
+    k_pal_compact<<<TAB_SLOTS / 256, 256, 0, c->stream>>>(t, ctl);
+    k_pal_rank<<<PAL_CAP / 256, 256, 0, c->stream>>>(t, ctl);
+    VHX_HIP(c, hipGetLastError());
+
+    // the one readback before allocation
+    BuildCtl h;
+    VHX_HIP(c, hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    VHX_HIP(c, hipStreamSynchronize(c->stream));
+    if (h.overflow || h.ncolors > MAX_COLORS)
+        return fail(c, VHX_E_CAPACITY, "vhx_build_tree_dense: more than 65535 distinct colours");
+    if (h.brick_total >= 0x80000000ull) return fail(c, VHX_E_CAPACITY, "vhx_build_tree_dense: 2^31 bricks or more");
+    uint64_t nodes = 0;
+    for (uint32_t lv = 0; lv < levels; ++lv) {
+        fa.level_base[lv] = (uint32_t)nodes;
+        nodes += h.level_total[lv];
+    }
+    if (nodes >= 0xFFFFFFFFull) return fail(c, VHX_E_CAPACITY, "vhx_build_tree_dense: 2^32 nodes or more");
+    fa.color_count = h.ncolors;
+    vhx_tree_desc counts{};
+    counts.boxtree_size = S;
+    counts.brick_dim = bd;
+    counts.node_count = (uint32_t)nodes;
+    counts.brick_count = (uint32_t)h.brick_total;
+    counts.color_count = h.ncolors;
+    return vhx::receive_tree(c, counts, fill_from_scratch, &fa);
+}
+
+int vhx_tree_counts(const vhx_ctx *c, vhx_tree_desc *counts) {
+    if (!c || !counts) return VHX_E_INVALID_ARG;
+    if (!c->tree->uploaded) return VHX_E_STATE;
+    *counts = c->tree->desc;  // its array pointers are null
+    return VHX_OK;
+}
+
+int vhx_read_range(vhx_ctx *c, int id, uint64_t off, uint64_t count, void *dst) {
+    if (!c || id < 0 || id > 6 || (!dst && count)) return VHX_E_INVALID_ARG;
+    if (!c->tree->uploaded) return fail(c, VHX_E_STATE, "vhx_read_range before vhx_upload_tree");
+    const uint64_t cap = vhx::elem_count(c->tree->desc, id), es = vhx::elem_size(id);
+    if (off > cap || count > cap - off) return fail(c, VHX_E_CAPACITY, "vhx_read_range: range beyond the uploaded buffer");
+    if (count == 0) return VHX_OK;
+    VHX_HIP(c, hipSetDevice(c->device));
+    VHX_STREAM(c);
+    vhx::TraceScope tscope(c);  // after the tree's last write
+    if (tscope.rc) return tscope.rc;
+    VHX_HIP(c, hipMemcpyAsync(dst, (const char *)c->tree->raw[id].ptr + off * es, count * es, hipMemcpyDeviceToHost,
+                              c->stream));
+    VHX_HIP(c, hipStreamSynchronize(c->stream));
+    return tscope.end();
+}
+
+}  // extern "C"

@@ -19,7 +19,7 @@ import math
 import numpy as np
 
 from . import _native as N
-from .boxtree import V3c, FlatTree
+from .boxtree import V3c, FlatTree, TreeImage, TREE_ARRAYS, _TREE_ERRORS
 
 f32 = np.float32
 _libm = ctypes.CDLL("libm.so.6")
@@ -181,6 +181,10 @@ def _ptr(a):
     return a.ctypes.data
 
 
+class _BuiltOnDevice:
+    """Stands for a context's tree that exists only on the device (Raytracer.build_dense)."""
+
+
 class Raytracer:
     """A libvhx context on one HIP device with a tree resident in HBM."""
 
@@ -236,6 +240,57 @@ class Raytracer:
             return
         self._check(N.lib().vhx_upload_tree(self._h, ctypes.byref(flat.desc)))
         self._tree = flat
+
+    def build_dense(self, grid, size, brick_dim):
+        """vhx_build_tree_dense: builds the canonical tree of a dense grid on the GPU and makes it this context's tree
+        (the image of FlatTree.from_dense + upload, bit for bit). `grid` has shape (gz, gy, gx) and holds packed albedos
+        r | g<<8 | b<<16 | a<<24, alpha 0 = no voxel: a uint32 numpy array (copied to the device first), or a contiguous
+        int32 / uint32 torch tensor on this context's device, read in place. The build runs on the context's stream,
+        not on torch's: for a tensor, torch's current stream on the device is synchronised before the call, so the
+        work that produced the grid has finished. The call returns when the tree is ready (download() reads it)."""
+        if hasattr(grid, "data_ptr"):
+            import torch
+            if not grid.is_cuda or grid.device.index != self.device:
+                raise ValueError(f"build_dense: the tensor must live on device {self.device}")
+            if grid.dim() != 3 or grid.dtype not in (torch.int32, torch.uint32) or not grid.is_contiguous():
+                raise TypeError("build_dense: a contiguous int32 / uint32 tensor of shape (gz, gy, gx)")
+            torch.cuda.current_stream(grid.device).synchronize()
+            d = N.DenseDesc()
+            d.boxtree_size, d.brick_dim = int(size), int(brick_dim)
+            d.gz, d.gy, d.gx = (int(v) for v in grid.shape)
+            d.albedo = grid.data_ptr()
+            on_device = 1
+        else:
+            from .boxtree import _dense_desc
+            d, grid = _dense_desc(grid, size, brick_dim)
+            on_device = 0
+        rc = N.lib().vhx_build_tree_dense(self._h, ctypes.byref(d), on_device)
+        if rc in _TREE_ERRORS:
+            raise _TREE_ERRORS[rc](f"size {size} brick_dim {brick_dim}")
+        self._check(rc)
+        self._tree = _BuiltOnDevice()
+
+    def tree_counts(self):
+        """vhx_tree_counts: sizes and counts of the uploaded tree."""
+        d = N.TreeDesc()
+        self._check(N.lib().vhx_tree_counts(self._h, ctypes.byref(d)))
+        return d
+
+    def read_range(self, buffer_id, elem_offset, elem_count):
+        """vhx_read_range: elements of one raw tree buffer (VHX_BUF_*) copied back from the device."""
+        a = np.empty(elem_count, TREE_ARRAYS[buffer_id][1])
+        self._check(N.lib().vhx_read_range(self._h, buffer_id, elem_offset, elem_count, a.ctypes.data))
+        return a
+
+    def download(self):
+        """The uploaded tree read back from the device (vhx_tree_counts + vhx_read_range): a TreeImage with the seven
+        arrays and the counts."""
+        d = self.tree_counts()
+        n3 = d.brick_dim ** 3
+        sizes = (d.node_count, d.node_count, d.node_count * 64, d.brick_count * n3, d.solid_count, d.color_count,
+                 d.data_count)
+        arrays = {name: self.read_range(i, 0, n) for i, ((name, _), n) in enumerate(zip(TREE_ARRAYS, sizes))}
+        return TreeImage(d.boxtree_size, d.brick_dim, arrays)
 
     def update_range(self, buffer_id, elem_offset, values):
         values = np.ascontiguousarray(values)
