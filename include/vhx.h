@@ -213,6 +213,12 @@ typedef struct vhx_dense_desc {
  * shared contexts trace the new tree afterwards), and like an upload it disables node MIPs. VHX_E_CAPACITY for more than
  * 65,535 distinct colours or 2^31 bricks or more; a failing build leaves the context's previous tree as it was. */
 int vhx_build_tree_dense(vhx_ctx *ctx, const vhx_dense_desc *grid, int on_device);
+/* The same with the tree simplified as the reference simplifies a loaded model (BoxTree::simplify(ROOT, recursive)): the
+ * seven buffers and counts of vhx_dense_build_simplified (vhx_boxtree.h) + vhx_upload_tree, bit for bit. Nodes, occupancy
+ * and palettes are those of vhx_build_tree_dense; a brick of one colour throughout becomes a Solid entry (solid_values),
+ * a leaf whose bricks are all the same Solid brick, or whose aligned 4x4x4 voxel blocks are all homogeneous, a
+ * UniformLeaf holding one brick. Contract, ordering and errors as vhx_build_tree_dense. */
+int vhx_build_tree_dense_simplified(vhx_ctx *ctx, const vhx_dense_desc *grid, int on_device);
 #define VHX_BUF_NODE_TYPE 0
 #define VHX_BUF_NODE_OCBITS 1
 #define VHX_BUF_NODE_CHILDREN 2

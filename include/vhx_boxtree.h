@@ -25,6 +25,7 @@
  *   vhx_scene_build            <- bulk builder producing exactly the flattened tree that inserting a procedural
  *                                 scene voxel by voxel (x, then y, then z loops) would produce
  *   vhx_dense_build            <- the same for a caller's dense voxel grid (vhx_dense_desc, vhx.h)
+ *   vhx_dense_build_simplified <- that tree after BoxTree::simplify(ROOT, recursive), as load_vox_file leaves a model
  *
  * Tree type parameter: T = u32 (the reference default, BoxTree<T = u32>, src/boxtree/types.rs:219).
  */
@@ -143,6 +144,12 @@ int vhx_dense_build(const vhx_dense_desc *grid, int threads, vhx_flat **out);
 /* The host BoxTree of that image (as vhx_scene_build_tree: occlusion bits and MIP maps not restored); inserts, clears,
  * MIPs and a stream continue from it. */
 int vhx_dense_build_tree(const vhx_dense_desc *grid, int threads, vhx_boxtree **out);
+/* The simplified image of a dense grid: vhx_dense_build_tree, vhx_boxtree_simplify(tree, recursive = 1) and
+ * vhx_boxtree_flatten in one call (no algorithm of its own). Nodes, occupancy and palettes are those of vhx_dense_build;
+ * the leaves hold Solid bricks where a brick is one colour throughout and become UniformLeaf nodes where all their bricks
+ * are the same Solid brick or every aligned 4x4x4 block of their voxels is homogeneous. vhx_build_tree_dense_simplified
+ * (vhx.h) writes the same image on the GPU. Errors as vhx_dense_build. */
+int vhx_dense_build_simplified(const vhx_dense_desc *grid, int threads, vhx_flat **out);
 int vhx_flat_node_mips(const vhx_flat *flat, const uint32_t **node_mips, uint32_t *count);
 /* Fills *desc with pointers into the flat object (valid until vhx_flat_free). */
 int vhx_flat_desc(const vhx_flat *flat, vhx_tree_desc *desc);

@@ -113,6 +113,7 @@ SIGNATURES = [
     ("vhx_upload_tree", c_int, [c_void_p, P(TreeDesc)]),
     ("vhx_upload_tree_device", c_int, [c_void_p, P(TreeDesc)]),
     ("vhx_build_tree_dense", c_int, [c_void_p, P(DenseDesc), c_int]),
+    ("vhx_build_tree_dense_simplified", c_int, [c_void_p, P(DenseDesc), c_int]),
     ("vhx_tree_counts", c_int, [c_void_p, P(TreeDesc)]),
     ("vhx_read_range", c_int, [c_void_p, c_int, c_u64, c_u64, c_void_p]),
     ("vhx_set_node_mips", c_int, [c_void_p, c_void_p, c_u32]),
@@ -186,6 +187,7 @@ SIGNATURES = [
     ("vhx_scene_build_tree", c_int, [c_u32, c_u32, c_u32, c_u64, c_int, P(c_void_p)]),
     ("vhx_dense_build", c_int, [P(DenseDesc), c_int, P(c_void_p)]),
     ("vhx_dense_build_tree", c_int, [P(DenseDesc), c_int, P(c_void_p)]),
+    ("vhx_dense_build_simplified", c_int, [P(DenseDesc), c_int, P(c_void_p)]),
     ("vhx_flat_desc", c_int, [c_void_p, P(TreeDesc)]),
     ("vhx_boxtree_switch_mips", c_int, [c_void_p, c_int]),
     ("vhx_boxtree_set_mip_method", c_int, [c_void_p, c_u32, c_u32, c_f32]),

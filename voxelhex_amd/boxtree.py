@@ -398,13 +398,15 @@ class FlatTree:
         return FlatTree(h.value)
 
     @staticmethod
-    def from_dense(grid, size, brick_dim, threads=0):
+    def from_dense(grid, size, brick_dim, threads=0, simplify=False):
         """Bulk-builds the canonical tree of a dense grid (vhx_dense_build): `grid` is a uint32 numpy array of shape
         (gz, gy, gx) of packed albedos r | g<<8 | b<<16 | a<<24 (alpha 0 = no voxel) sitting at the tree's origin. The
-        image equals inserting every voxel (x outer, y, z inner) into BoxTree(size, brick_dim) and flattening."""
+        image equals inserting every voxel (x outer, y, z inner) into BoxTree(size, brick_dim) and flattening; with
+        simplify=True, simplifying the tree recursively before flattening (vhx_dense_build_simplified)."""
         d, keep = _dense_desc(grid, size, brick_dim)
         h = ctypes.c_void_p()
-        _tree_check(N.lib().vhx_dense_build(ctypes.byref(d), threads, ctypes.byref(h)),
+        build = N.lib().vhx_dense_build_simplified if simplify else N.lib().vhx_dense_build
+        _tree_check(build(ctypes.byref(d), threads, ctypes.byref(h)),
                     f"dense grid {keep.shape[::-1]} size {size} brick_dim {brick_dim}")
         return FlatTree(h.value)
 

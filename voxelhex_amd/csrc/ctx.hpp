@@ -126,9 +126,10 @@ struct vhx_ctx {
     // vhx_build_tree_dense (vhx_build.hip): scratch kept across builds and reset by each one -- the occupancy words of
     // every possible node per level (the leaves' are their brick masks), their breadth-first ranks and first brick
     // indices, the scans' block sums, the colour table with the palette ranked from it, the counters read back, and the
-    // device copy of a host grid
+    // device copy of a host grid; for vhx_build_tree_dense_simplified also the leaves' Parted masks and classes and the
+    // ranked solid values (simp)
     struct BuildScratch {
-        DevBuf occ, rank, first, part, table, ctl, grid;
+        DevBuf occ, rank, first, part, table, ctl, grid, simp;
     } build;
     // depth-prepass mode (vhx_set_depth_prepass; opt-in, not the reference path)
     bool prepass = false, in_prepass = false;

@@ -12,6 +12,8 @@
 // insert.rs:428-449). vhx_scene_build writes that canonical image directly; tests check it buffer-equal against
 // vhx_scene_insert + vhx_boxtree_flatten. The image is a pure function of the voxels, so the same builder takes a caller's
 // dense grid (vhx_dense_build); vhx_build_tree_dense (vhx_build.hip) writes the same image on the GPU.
+// vhx_dense_build_simplified is that tree simplified recursively and flattened: the image
+// vhx_build_tree_dense_simplified is held to.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -766,6 +768,24 @@ int vhx_dense_build_tree(const vhx_dense_desc *grid, int threads, vhx_boxtree **
         BoxTree *t = tree_of_flat(*full);
         if (!t) return VHX_E_STATE;
         *out = new vhx_boxtree{t};
+        return VHX_OK;
+    } catch (const std::bad_alloc &) {
+        return VHX_E_CAPACITY;
+    }
+}
+int vhx_dense_build_simplified(const vhx_dense_desc *grid, int threads, vhx_flat **out) {
+    if (!out) return VHX_E_INVALID_ARG;
+    *out = nullptr;
+    try {
+        vhx_flat *full = nullptr;
+        int rc = build_dense(grid, threads, &full);
+        if (rc != VHX_OK) return rc;
+        std::unique_ptr<vhx_flat> owned(full);
+        std::unique_ptr<BoxTree> t(tree_of_flat(*full));
+        if (!t) return VHX_E_STATE;
+        owned.reset();
+        t->simplify(0, true);
+        *out = flatten_tree(*t);
         return VHX_OK;
     } catch (const std::bad_alloc &) {
         return VHX_E_CAPACITY;

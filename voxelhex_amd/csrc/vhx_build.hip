@@ -20,10 +20,30 @@
 //   fill     k_emit_nodes      node types, occupancy and children, level by level, into the tree's raw buffers
 //            k_emit_bricks     the cells of every present brick gathered from the grid and translated through the table
 //
-// Every atomic is an OR, a minimum, a constant store or the claim of a table slot, and every order that reaches a
-// buffer comes from a scan or from the first indices, so the buffers do not depend on scheduling. Grid offsets are
+// Every atomic is an OR, a minimum, a constant store, the claim of a table slot or the count of such events (colours
+// claimed, entries compacted, solid values: only the total is used), and every order that reaches a buffer comes from a
+// scan or from the first indices, so the buffers do not depend on scheduling. Grid offsets are
 // 64-bit; nothing outside [0,gx) x [0,gy) x [0,gz) is read.
+//
+// vhx_build_tree_dense_simplified writes the image BoxTree::simplify(ROOT, recursive) leaves of that tree
+// (vhx_dense_build_simplified of flatten.cpp, bit for bit). Nodes, their numbering, occupancy and the palette stay;
+// only the leaves change. A brick all of whose cells hold one colour is Solid(palette index | 0xFFFF0000); a leaf whose
+// 64 bricks are the same Solid brick is a UniformLeaf with that descriptor as entry 0; otherwise, with brick_dim > 1, a
+// leaf whose aligned 4x4x4 voxel blocks are all homogeneous (one colour, or empty) is a UniformLeaf with one Parted brick
+// holding the blocks' values; every other leaf keeps per-sectant entries: empty, Solid, or a brick index. Only Parted
+// bricks are numbered, and solid_values lists the distinct Solid values by their first (leaf, sectant). The plain passes
+// run unchanged up to the palette; then, in place of the brick scan:
+//   classify k_classify        one workgroup per present leaf reads its voxels once more: a lane ORs a brick's "not solid"
+//                              bit where a cell differs from the brick's corner cell (or is empty) and a "not
+//                              block-uniform" flag where a voxel differs from its block's corner voxel; OR inside the
+//                              wave, then in LDS. The leaf's class, its mask of Parted bricks and their count follow, and
+//                              every Solid entry's colour takes the minimum of its key leaf_code * 64 + sectant
+//   scan     k_scan_*          MODE 2: the leaf's first brick index from the Parted counts
+//   rank     k_solid_rank      the keys ranked as k_pal_rank ranks first indices: solid_values and each colour's index
+//   fill     k_emit_leaves     leaf types and entries by class; k_emit_bricks over the Parted masks;
+//            k_emit_uniform    the one brick of a block-uniform leaf, sampled at the block corners
 #include <algorithm>
+#include <string>
 
 #include "../../include/vhx_boxtree.h"
 #include "ctx.hpp"
@@ -36,6 +56,9 @@ constexpr uint32_t TAB_SLOTS = 1u << 18;  // four times the colours a palette ho
 constexpr uint32_t TAB_MASK = TAB_SLOTS - 1;
 constexpr uint32_t MAX_COLORS = 0xFFFFu;  // the palette index has 16 bits, 0xFFFF = none
 constexpr uint32_t PAL_CAP = 1u << 16;
+// color_lookup answers 0xFFFF for a colour the table does not hold (a build whose table overflowed, which fails at the
+// readback): arrays indexed by palette index have PAL_CAP entries, so that index stays inside them
+static_assert(PAL_CAP > MAX_COLORS, "a palette index, 0xFFFF = none included, must index a PAL_CAP array");
 constexpr uint32_t MAX_LEVELS = 8;
 constexpr uint64_t MAX_LEAVES = 1ull << 28;  // possible leaf nodes (scratch words per array)
 constexpr uint32_t SCAN_ITEMS = 4, SCAN_TILE = 256 * SCAN_ITEMS;
@@ -48,7 +71,7 @@ struct BuildCtl {
     uint32_t ncolors;   // table slots claimed
     uint32_t overflow;  // more than MAX_COLORS colours
     uint32_t ncompact;
-    uint32_t pad;
+    uint32_t solid_count;  // simplified build: distinct Solid values
 };
 
 // vhx_ctx::build.table
@@ -74,6 +97,28 @@ ColorTable table_of(void *base) {
     t.pal = t.cslot + PAL_CAP;
     return t;
 }
+
+// vhx_ctx::build.simp (simplified build)
+struct SimpTable {
+    u64 *pmask;       // [nleaf]   the leaf's Parted bricks (0 for a UniformLeaf)
+    u64 *linfo;       // [nleaf]   bits 0..6 bricks the leaf contributes, bits 8..9 its class (LEAF_*)
+    u64 *skey;        // [PAL_CAP] by palette index: smallest leaf_code * 64 + sectant of a Solid entry of the colour
+    uint32_t *srank;  // [PAL_CAP] by palette index: the colour's index in solid_values
+    uint32_t *svals;  // [PAL_CAP] solid_values
+};
+constexpr uint64_t SKEY_BYTES = (uint64_t)PAL_CAP * 8;
+inline uint64_t simp_bytes(uint64_t nleaf) { return nleaf * 16 + SKEY_BYTES + 2ull * PAL_CAP * 4; }
+SimpTable simp_of(void *base, uint64_t nleaf) {
+    SimpTable sp;
+    uint8_t *p = (uint8_t *)base;
+    sp.pmask = (u64 *)p;
+    sp.linfo = sp.pmask + nleaf;
+    sp.skey = sp.linfo + nleaf;
+    sp.srank = (uint32_t *)(sp.skey + PAL_CAP);
+    sp.svals = sp.srank + PAL_CAP;
+    return sp;
+}
+constexpr uint32_t LEAF_PLAIN = 0, LEAF_UNIFORM_SOLID = 1, LEAF_UNIFORM_PARTED = 2;
 
 struct GridP {
     const uint32_t *a;
@@ -226,9 +271,10 @@ __global__ __launch_bounds__(256) void k_reduce_level(const u64 *child, u64 *par
 }
 
 // ---- scans over the occupancy words of a level: MODE 0 "the node exists" (the root always does), MODE 1 its bricks
+// (MODE 2: of a simplified build, from SimpTable::linfo)
 template <int MODE>
 __device__ inline uint32_t scan_value(u64 w, bool root) {
-    return MODE == 0 ? (uint32_t)(w != 0 || root) : (uint32_t)__popcll(w);
+    return MODE == 0 ? (uint32_t)(w != 0 || root) : MODE == 1 ? (uint32_t)__popcll(w) : (uint32_t)(w & 0x7Fu);
 }
 
 // inclusive scan over the block's 256 threads (lds: 4 words)
@@ -394,9 +440,181 @@ __global__ __launch_bounds__(256) void k_emit_bricks(GridP g, const u64 *leaf_ma
     }
 }
 
+// ---- the simplified image
+// voxel (x, y, z) of the tree: 0 outside the grid and for alpha 0
+__device__ inline uint32_t grid_at(const GridP &g, uint32_t x, uint32_t y, uint32_t z) {
+    if (x >= g.gx || y >= g.gy || z >= g.gz) return 0;
+    const uint32_t c = g.a[((uint64_t)z * g.gy + y) * g.gx + x];
+    return (c >> 24) ? c : 0u;
+}
+
+// leaf coordinates of a path code
+__device__ inline void leaf_coord(uint64_t code, uint32_t D, uint32_t &lx, uint32_t &ly, uint32_t &lz) {
+    lx = ly = lz = 0;
+    for (uint32_t i = 0; i < D; ++i) {
+        const uint32_t d = (uint32_t)(code >> (6 * i)) & 63u;
+        lx |= (d & 3u) << (2 * i);
+        ly |= ((d >> 2) & 3u) << (2 * i);
+        lz |= (d >> 4) << (2 * i);
+    }
+}
+
+// One block per present leaf at a time. Both tests compare a voxel with a fixed corner, so a lane only ever ORs: bit s
+// of `ns` where a cell of brick s differs from the brick's corner cell or is empty (the brick is not Solid), `nb` where
+// a voxel differs from the corner of its aligned 4x4x4 block. The loop bounds are the same for every thread of a block,
+// so the wave operations run with all 64 lanes.
+__global__ __launch_bounds__(256) void k_classify(GridP g, const u64 *leaf_mask, uint64_t nleaf, ColorTable t,
+                                                  SimpTable sp) {
+    __shared__ u64 s_ns;
+    __shared__ uint32_t s_nb;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t lsh = g.bsh + 2, L = 1u << lsh, nvox = 1u << (3 * lsh);
+    for (uint64_t code = blockIdx.x; code < nleaf; code += gridDim.x) {
+        const u64 m = leaf_mask[code];
+        if (m == 0) continue;  // the whole block
+        if (tid == 0) {
+            s_ns = 0;
+            s_nb = 0;
+        }
+        __syncthreads();
+        uint32_t lx, ly, lz;
+        leaf_coord(code, g.D, lx, ly, lz);
+        const uint32_t ox = lx << lsh, oy = ly << lsh, oz = lz << lsh;
+        u64 ns = 0;
+        bool nb = false;
+        for (uint32_t j = tid; j < nvox; j += 256) {
+            const uint32_t x = j & (L - 1u), y = (j >> lsh) & (L - 1u), z = j >> (2 * lsh);
+            const uint32_t c = grid_at(g, ox + x, oy + y, oz + z);
+            const uint32_t bx = x >> g.bsh, by = y >> g.bsh, bz = z >> g.bsh;
+            const uint32_t cb = grid_at(g, ox + (bx << g.bsh), oy + (by << g.bsh), oz + (bz << g.bsh));
+            const uint32_t ck = grid_at(g, ox + (x & ~3u), oy + (y & ~3u), oz + (z & ~3u));
+            if (c == 0 || c != cb) ns |= 1ull << (bx | (by << 2) | (bz << 4));
+            nb = nb || c != ck;
+        }
+#pragma unroll
+        for (uint32_t k = 1; k < 64; k <<= 1) ns |= __shfl_xor(ns, k);
+        const bool wave_nb = __ballot(nb) != 0;
+        if (lane == 0) {
+            if (ns) atomicOr(&s_ns, ns);
+            if (wave_nb) atomicOr(&s_nb, 1u);
+        }
+        __syncthreads();
+        if (tid < 64) {  // wave 0: a lane per sectant
+            const u64 solid = m & ~s_ns;
+            const uint32_t cs = grid_at(g, ox + ((tid & 3u) << g.bsh), oy + (((tid >> 2) & 3u) << g.bsh),
+                                        oz + ((tid >> 4) << g.bsh));  // the colour of a Solid brick
+            const bool one_value = __ballot(cs == __shfl(cs, 0)) == ~0ull;
+            uint32_t cls = LEAF_PLAIN;
+            if (solid == ~0ull && one_value)
+                cls = LEAF_UNIFORM_SOLID;
+            else if (g.bsh > 0 && s_nb == 0)
+                cls = LEAF_UNIFORM_PARTED;
+            const u64 pm = cls == LEAF_PLAIN ? m & ~solid : 0ull;
+            if (tid == 0) {
+                sp.pmask[code] = pm;
+                sp.linfo[code] = (u64)(cls == LEAF_UNIFORM_PARTED ? 1u : (uint32_t)__popcll(pm)) | ((u64)cls << 8);
+            }
+            // the Solid entries the leaf will hold: the lowest sectant of a colour records it for the leaf
+            const bool cand = ((solid >> tid) & 1ull) && (cls == LEAF_PLAIN || (cls == LEAF_UNIFORM_SOLID && tid == 0));
+            const uint32_t idx = cand ? color_lookup(t, cs) : 0xFFFFu;
+            u64 pending = __ballot(cand);
+            while (pending) {  // the same in every lane
+                const uint32_t leader = (uint32_t)__ffsll((long long)pending) - 1u;
+                const uint32_t li = __shfl(idx, leader);
+                if (lane == leader) {
+                    const u64 key = code * 64ull + tid;
+                    if (sp.skey[idx] > key) atomicMin(&sp.skey[idx], key);  // as color_insert
+                }
+                pending &= ~__ballot(cand && idx == li);
+            }
+        }
+        __syncthreads();  // s_ns and s_nb are reset for the next leaf
+    }
+}
+
+// index of a colour in solid_values = how many colours have a smaller key (keys of used colours are distinct, an unused
+// colour's is ~0); their number is the solid count
+__global__ __launch_bounds__(256) void k_solid_rank(SimpTable sp, BuildCtl *ctl) {
+    __shared__ u64 tile[256];
+    const uint32_t n = min(ctl->ncolors, MAX_COLORS);
+    if (blockIdx.x * 256u >= n) return;  // the whole block
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    const u64 mine = i < n ? sp.skey[i] : ~0ull;
+    uint32_t rank = 0;
+    for (uint32_t j0 = 0; j0 < n; j0 += 256) {
+        tile[threadIdx.x] = j0 + threadIdx.x < n ? sp.skey[j0 + threadIdx.x] : ~0ull;
+        __syncthreads();
+        const uint32_t m = min(256u, n - j0);
+        for (uint32_t j = 0; j < m; ++j) rank += tile[j] < mine;
+        __syncthreads();
+    }
+    const bool used = mine != ~0ull;
+    if (used) {
+        sp.srank[i] = rank;
+        sp.svals[rank] = i | 0xFFFF0000u;  // pix_visual: colour index, no data
+    }
+    const u64 b = __ballot(used);
+    if ((threadIdx.x & 63u) == 0 && b) atomicAdd(&ctl->solid_count, (uint32_t)__popcll(b));
+}
+
+// k_emit_nodes for the leaf level of a simplified image: one thread per (possible leaf c, sectant s)
+__global__ __launch_bounds__(256) void k_emit_leaves(GridP g, uint64_t n, const u64 *occ, const u64 *rank,
+                                                     const u64 *first, uint32_t base, ColorTable t, SimpTable sp,
+                                                     uint32_t *node_type, u64 *node_ocbits, uint32_t *node_children) {
+    const uint64_t gid = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint64_t c = gid >> 6;
+    const uint32_t s = (uint32_t)gid & 63u;
+    if (c >= n) return;
+    const u64 w = occ[c];
+    if (w == 0 && g.D != 0) return;  // no such node
+    const uint64_t ni = (uint64_t)base + rank[c];
+    const uint32_t cls = (uint32_t)(sp.linfo[c] >> 8) & 3u;
+    if (s == 0) {
+        node_type[ni] = w ? (cls == LEAF_PLAIN ? VHX_NODE_LEAF : VHX_NODE_UNIFORM_LEAF) : VHX_NODE_NOTHING;
+        node_ocbits[ni] = w;
+    }
+    uint32_t child = VHX_EMPTY;
+    if (cls == LEAF_UNIFORM_PARTED) {
+        if (s == 0) child = (uint32_t)first[c];
+    } else if (((w >> s) & 1ull) && (cls == LEAF_PLAIN || s == 0)) {
+        const u64 pm = sp.pmask[c];
+        if ((pm >> s) & 1ull) {
+            child = (uint32_t)(first[c] + (u64)__popcll(pm & ((1ull << s) - 1ull)));
+        } else {
+            uint32_t lx, ly, lz;
+            leaf_coord(c, g.D, lx, ly, lz);
+            const uint32_t lsh = g.bsh + 2;
+            const uint32_t cs = grid_at(g, (lx << lsh) + ((s & 3u) << g.bsh), (ly << lsh) + (((s >> 2) & 3u) << g.bsh),
+                                        (lz << lsh) + ((s >> 4) << g.bsh));
+            child = VHX_SOLID_BIT | sp.srank[color_lookup(t, cs)];
+        }
+    }
+    node_children[ni * 64 + s] = child;
+}
+
+// The one brick of every block-uniform leaf: cell (x, y, z) is the value of the leaf's block (x, y, z), read at the
+// block's corner voxel.
+__global__ __launch_bounds__(256) void k_emit_uniform(GridP g, const u64 *first, uint64_t nleaf, ColorTable t,
+                                                      SimpTable sp, uint32_t *voxels) {
+    const uint32_t bd = 1u << g.bsh, n3sh = 3 * g.bsh, lsh = g.bsh + 2;
+    for (uint64_t code = blockIdx.x; code < nleaf; code += gridDim.x) {
+        if (((uint32_t)(sp.linfo[code] >> 8) & 3u) != LEAF_UNIFORM_PARTED) continue;  // the whole block
+        uint32_t lx, ly, lz;
+        leaf_coord(code, g.D, lx, ly, lz);
+        uint32_t *dst = voxels + (first[code] << n3sh);
+        for (uint32_t i = threadIdx.x; i < (1u << n3sh); i += 256) {
+            const uint32_t c = grid_at(g, (lx << lsh) + ((i & (bd - 1u)) << 2), (ly << lsh) + (((i >> g.bsh) & (bd - 1u)) << 2),
+                                       (lz << lsh) + ((i >> (2 * g.bsh)) << 2));
+            dst[i] = c ? (color_lookup(t, c) | 0xFFFF0000u) : VHX_EMPTY;
+        }
+    }
+}
+
 struct FillArg {
     vhx_ctx *c;
     GridP g;
+    bool simplified;
+    uint32_t solid_count;
     uint32_t levels;
     uint64_t level_off[MAX_LEVELS];
     uint32_t level_base[MAX_LEVELS];
@@ -413,21 +631,34 @@ int fill_from_scratch(void *arg, void *const dst[7], const uint64_t bytes[7]) {
     const u64 *first = (const u64 *)c->build.first.ptr;
     const ColorTable t = table_of(c->build.table.ptr);
     const uint32_t D = a.levels - 1;
+    const uint64_t nleaf = 1ull << (6 * D);
+    const SimpTable sp = a.simplified ? simp_of(c->build.simp.ptr, nleaf) : SimpTable{};
     for (uint32_t lv = 0; lv <= D; ++lv) {
         const uint64_t n = 1ull << (6 * lv);
         const uint64_t child_off = lv < D ? a.level_off[lv + 1] : 0;
-        k_emit_nodes<<<blocks_for(n * 64), 256, 0, c->stream>>>(
-            lv, D, n, occ + a.level_off[lv], rank + a.level_off[lv], rank + child_off, first, a.level_base[lv],
-            lv < D ? a.level_base[lv + 1] : 0u, (uint32_t *)dst[VHX_BUF_NODE_TYPE], (u64 *)dst[VHX_BUF_NODE_OCBITS],
-            (uint32_t *)dst[VHX_BUF_NODE_CHILDREN]);
+        if (a.simplified && lv == D)
+            k_emit_leaves<<<blocks_for(n * 64), 256, 0, c->stream>>>(
+                a.g, n, occ + a.level_off[lv], rank + a.level_off[lv], first, a.level_base[lv], t, sp,
+                (uint32_t *)dst[VHX_BUF_NODE_TYPE], (u64 *)dst[VHX_BUF_NODE_OCBITS], (uint32_t *)dst[VHX_BUF_NODE_CHILDREN]);
+        else
+            k_emit_nodes<<<blocks_for(n * 64), 256, 0, c->stream>>>(
+                lv, D, n, occ + a.level_off[lv], rank + a.level_off[lv], rank + child_off, first, a.level_base[lv],
+                lv < D ? a.level_base[lv + 1] : 0u, (uint32_t *)dst[VHX_BUF_NODE_TYPE], (u64 *)dst[VHX_BUF_NODE_OCBITS],
+                (uint32_t *)dst[VHX_BUF_NODE_CHILDREN]);
     }
     VHX_HIP(c, hipGetLastError());
     if (bytes[VHX_BUF_VOXELS]) {
-        const uint64_t nleaf = 1ull << (6 * D);
-        k_emit_bricks<<<(unsigned)std::min<uint64_t>(nleaf, (uint64_t)c->cus * 16), 256, 0, c->stream>>>(
-            a.g, occ + a.level_off[D], first, nleaf, t, (uint32_t *)dst[VHX_BUF_VOXELS]);
+        const unsigned blocks = (unsigned)std::min<uint64_t>(nleaf, (uint64_t)c->cus * 16);
+        // a simplified image copies the Parted bricks only
+        k_emit_bricks<<<blocks, 256, 0, c->stream>>>(a.g, a.simplified ? sp.pmask : occ + a.level_off[D], first, nleaf, t,
+                                                     (uint32_t *)dst[VHX_BUF_VOXELS]);
+        if (a.simplified && a.g.bsh > 0)
+            k_emit_uniform<<<blocks, 256, 0, c->stream>>>(a.g, first, nleaf, t, sp, (uint32_t *)dst[VHX_BUF_VOXELS]);
         VHX_HIP(c, hipGetLastError());
     }
+    if (bytes[VHX_BUF_SOLID_VALUES])
+        VHX_HIP(c, hipMemcpyAsync(dst[VHX_BUF_SOLID_VALUES], sp.svals, (uint64_t)a.solid_count * 4,
+                                  hipMemcpyDeviceToDevice, c->stream));
     if (bytes[VHX_BUF_COLOR_PALETTE])
         VHX_HIP(c, hipMemcpyAsync(dst[VHX_BUF_COLOR_PALETTE], t.pal, (uint64_t)a.color_count * 4,
                                   hipMemcpyDeviceToDevice, c->stream));
@@ -445,24 +676,22 @@ int scan_level(vhx_ctx *c, const u64 *occ, uint64_t n, bool root, u64 *out, u64 
     return VHX_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int vhx_build_tree_dense(vhx_ctx *c, const vhx_dense_desc *grid, int on_device) {
-    if (!c || !grid) return fail(c, VHX_E_INVALID_ARG, "vhx_build_tree_dense: null argument");
-    if (c->shared) return fail(c, VHX_E_STATE, "vhx_build_tree_dense on a shared context: build through the owner");
+// both entry points; `name` is the one called, for the error texts
+int build_tree(vhx_ctx *c, const vhx_dense_desc *grid, int on_device, bool simplified, const char *name) {
+    const auto fail_in = [&](int code, const char *what) { return fail(c, code, std::string(name) + what); };
+    if (!c || !grid) return fail_in(VHX_E_INVALID_ARG, ": null argument");
+    if (c->shared) return fail_in(VHX_E_STATE, " on a shared context: build through the owner");
     {
         vhx_boxtree *probe = nullptr;  // the validity rules of BoxTree::new
         const int rc = vhx_boxtree_new(grid->boxtree_size, grid->brick_dim, &probe);
-        if (rc) return fail(c, rc, "vhx_build_tree_dense: invalid boxtree_size / brick_dim");
+        if (rc) return fail_in(rc, ": invalid boxtree_size / brick_dim");
         vhx_boxtree_free(probe);
     }
     const uint32_t S = grid->boxtree_size, bd = grid->brick_dim;
     if (!grid->albedo || grid->gx == 0 || grid->gy == 0 || grid->gz == 0 || grid->gx > S || grid->gy > S || grid->gz > S)
-        return fail(c, VHX_E_INVALID_ARG, "vhx_build_tree_dense: null grid, or an extent of 0 or above boxtree_size");
+        return fail_in(VHX_E_INVALID_ARG, ": null grid, or an extent of 0 or above boxtree_size");
     if ((bd & (bd - 1)) != 0 || (S & (S - 1)) != 0 || S < 4 * bd)
-        return fail(c, VHX_E_INVALID_ARG, "vhx_build_tree_dense: sizes must be powers of two");
+        return fail_in(VHX_E_INVALID_ARG, ": sizes must be powers of two");
     GridP g{};
     g.gx = grid->gx;
     g.gy = grid->gy;
@@ -471,14 +700,15 @@ int vhx_build_tree_dense(vhx_ctx *c, const vhx_dense_desc *grid, int on_device) 
     const uint32_t nl = S / (4 * bd);  // leaf nodes per axis = 4^D
     while ((1u << (2 * g.D)) < nl) ++g.D;
     if ((1u << (2 * g.D)) != nl)
-        return fail(c, VHX_E_INVALID_ARG, "vhx_build_tree_dense: boxtree_size is not brick_dim * 4^k");
+        return fail_in(VHX_E_INVALID_ARG, ": boxtree_size is not brick_dim * 4^k");
     const uint32_t D = g.D, levels = D + 1;
     const uint64_t nleaf = 1ull << (6 * D);
     if (levels > MAX_LEVELS || nleaf > MAX_LEAVES)
-        return fail(c, VHX_E_CAPACITY, "vhx_build_tree_dense: more than 2^28 possible leaf nodes");
+        return fail_in(VHX_E_CAPACITY, ": more than 2^28 possible leaf nodes");
     FillArg fa{};
     fa.c = c;
     fa.levels = levels;
+    fa.simplified = simplified;
     uint64_t words = 0;
     for (uint32_t lv = 0; lv < levels; ++lv) {
         fa.level_off[lv] = words;
@@ -496,6 +726,7 @@ int vhx_build_tree_dense(vhx_ctx *c, const vhx_dense_desc *grid, int on_device) 
     if ((rc = vhx::ensure(c, c->build.part, ((nleaf + SCAN_TILE - 1) / SCAN_TILE) * 8))) return rc;
     if ((rc = vhx::ensure(c, c->build.table, TAB_BYTES))) return rc;
     if ((rc = vhx::ensure(c, c->build.ctl, sizeof(BuildCtl)))) return rc;
+    if (simplified && (rc = vhx::ensure(c, c->build.simp, simp_bytes(nleaf)))) return rc;
     const uint64_t voxels = (uint64_t)g.gx * g.gy * g.gz;
     if (on_device) {
         g.a = grid->albedo;
@@ -513,6 +744,11 @@ int vhx_build_tree_dense(vhx_ctx *c, const vhx_dense_desc *grid, int on_device) 
     VHX_HIP(c, hipMemsetAsync(ctl, 0, sizeof(BuildCtl), c->stream));
     VHX_HIP(c, hipMemsetAsync(t.keys, 0, TAB_KEYS_BYTES, c->stream));
     VHX_HIP(c, hipMemsetAsync(t.vals, 0xFF, TAB_VALS_BYTES, c->stream));
+    const SimpTable sp = simplified ? simp_of(c->build.simp.ptr, nleaf) : SimpTable{};
+    if (simplified) {  // absent leaves have no bricks; no colour has a Solid entry yet
+        VHX_HIP(c, hipMemsetAsync(sp.pmask, 0, nleaf * 16, c->stream));
+        VHX_HIP(c, hipMemsetAsync(sp.skey, 0xFF, SKEY_BYTES, c->stream));
+    }
 
     // pass A
     {
@@ -539,33 +775,55 @@ int vhx_build_tree_dense(vhx_ctx *c, const vhx_dense_desc *grid, int on_device) 
         if ((rc = scan_level<0>(c, occ + fa.level_off[lv], 1ull << (6 * lv), lv == 0, rank + fa.level_off[lv],
                                 &ctl->level_total[lv])))
             return rc;
-    if ((rc = scan_level<1>(c, occ + fa.level_off[D], nleaf, false, first, &ctl->brick_total))) return rc;
+    if (!simplified && (rc = scan_level<1>(c, occ + fa.level_off[D], nleaf, false, first, &ctl->brick_total))) return rc;
     // palette
     k_pal_compact<<<TAB_SLOTS / 256, 256, 0, c->stream>>>(t, ctl);
     k_pal_rank<<<PAL_CAP / 256, 256, 0, c->stream>>>(t, ctl);
     VHX_HIP(c, hipGetLastError());
+    if (simplified) {  // leaf classes, the first brick of every leaf from its Parted bricks, the solid values
+        k_classify<<<(unsigned)std::min<uint64_t>(nleaf, (uint64_t)c->cus * 16), 256, 0, c->stream>>>(
+            g, occ + fa.level_off[D], nleaf, t, sp);
+        VHX_HIP(c, hipGetLastError());
+        if ((rc = scan_level<2>(c, sp.linfo, nleaf, false, first, &ctl->brick_total))) return rc;
+        k_solid_rank<<<PAL_CAP / 256, 256, 0, c->stream>>>(sp, ctl);
+        VHX_HIP(c, hipGetLastError());
+    }
 
     // the one readback before allocation
     BuildCtl h;
     VHX_HIP(c, hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     VHX_HIP(c, hipStreamSynchronize(c->stream));
     if (h.overflow || h.ncolors > MAX_COLORS)
-        return fail(c, VHX_E_CAPACITY, "vhx_build_tree_dense: more than 65535 distinct colours");
-    if (h.brick_total >= 0x80000000ull) return fail(c, VHX_E_CAPACITY, "vhx_build_tree_dense: 2^31 bricks or more");
+        return fail_in(VHX_E_CAPACITY, ": more than 65535 distinct colours");
+    if (h.brick_total >= 0x80000000ull) return fail_in(VHX_E_CAPACITY, ": 2^31 bricks or more");
     uint64_t nodes = 0;
     for (uint32_t lv = 0; lv < levels; ++lv) {
         fa.level_base[lv] = (uint32_t)nodes;
         nodes += h.level_total[lv];
     }
-    if (nodes >= 0xFFFFFFFFull) return fail(c, VHX_E_CAPACITY, "vhx_build_tree_dense: 2^32 nodes or more");
+    if (nodes >= 0xFFFFFFFFull) return fail_in(VHX_E_CAPACITY, ": 2^32 nodes or more");
     fa.color_count = h.ncolors;
+    fa.solid_count = simplified ? h.solid_count : 0u;
     vhx_tree_desc counts{};
     counts.boxtree_size = S;
     counts.brick_dim = bd;
     counts.node_count = (uint32_t)nodes;
     counts.brick_count = (uint32_t)h.brick_total;
+    counts.solid_count = fa.solid_count;
     counts.color_count = h.ncolors;
     return vhx::receive_tree(c, counts, fill_from_scratch, &fa);
+}
+
+}  // namespace
+
+extern "C" {
+
+int vhx_build_tree_dense(vhx_ctx *c, const vhx_dense_desc *grid, int on_device) {
+    return build_tree(c, grid, on_device, false, "vhx_build_tree_dense");
+}
+
+int vhx_build_tree_dense_simplified(vhx_ctx *c, const vhx_dense_desc *grid, int on_device) {
+    return build_tree(c, grid, on_device, true, "vhx_build_tree_dense_simplified");
 }
 
 int vhx_tree_counts(const vhx_ctx *c, vhx_tree_desc *counts) {

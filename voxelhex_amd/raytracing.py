@@ -241,9 +241,10 @@ class Raytracer:
         self._check(N.lib().vhx_upload_tree(self._h, ctypes.byref(flat.desc)))
         self._tree = flat
 
-    def build_dense(self, grid, size, brick_dim):
+    def build_dense(self, grid, size, brick_dim, simplify=False):
         """vhx_build_tree_dense: builds the canonical tree of a dense grid on the GPU and makes it this context's tree
-        (the image of FlatTree.from_dense + upload, bit for bit). `grid` has shape (gz, gy, gx) and holds packed albedos
+        (the image of FlatTree.from_dense + upload, bit for bit); with simplify=True the simplified tree
+        (vhx_build_tree_dense_simplified, the image of FlatTree.from_dense(simplify=True)). `grid` has shape (gz, gy, gx) and holds packed albedos
         r | g<<8 | b<<16 | a<<24, alpha 0 = no voxel: a uint32 numpy array (copied to the device first), or a contiguous
         int32 / uint32 torch tensor on this context's device, read in place. The build runs on the context's stream,
         not on torch's: for a tensor, torch's current stream on the device is synchronised before the call, so the
@@ -264,7 +265,8 @@ class Raytracer:
             from .boxtree import _dense_desc
             d, grid = _dense_desc(grid, size, brick_dim)
             on_device = 0
-        rc = N.lib().vhx_build_tree_dense(self._h, ctypes.byref(d), on_device)
+        build = N.lib().vhx_build_tree_dense_simplified if simplify else N.lib().vhx_build_tree_dense
+        rc = build(self._h, ctypes.byref(d), on_device)
         if rc in _TREE_ERRORS:
             raise _TREE_ERRORS[rc](f"size {size} brick_dim {brick_dim}")
         self._check(rc)
