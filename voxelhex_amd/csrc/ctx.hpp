@@ -1,4 +1,5 @@
-// Internal context of libvhx (shared by the translation units of the device side: vhx_device.hip, vhx_mgpu.hip).
+// Internal context of libvhx, shared by the translation units of the device side: vhx_device.hip (tracing), vhx_tree.hip
+// (the device tree), vhx_ctx.hip (contexts, ordering, settings), vhx_mgpu.hip and vhx_build.hip.
 // Not part of the ABI: callers see vhx_ctx only as an opaque pointer (include/vhx.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -290,6 +291,8 @@ uint64_t elem_count(const vhx_tree_desc &d, int id);
 int alloc_tree(vhx_ctx *c, const vhx_tree_desc *t);
 // derives the device-side layout (node headers, brick bitmaps, child records) from the raw buffers, synchronously
 int finish_upload(vhx_ctx *c);
+// rebuilds DevTree::child_rec on c's stream when an update left it stale (every trace calls it before its first launch)
+int refresh_child_rec(vhx_ctx *c);
 // k_untile_planes on `stream` (arguments as vhx_untile_frame, already validated)
 int launch_untile(vhx_ctx *c, hipStream_t stream, const void *gathered, uint32_t planes, uint32_t ranks,
                   uint32_t tiles_per_rank, uint32_t T, uint32_t width, uint32_t height, uint32_t *fb_rgba,

@@ -1,13 +1,18 @@
-// libvhx device side: HIP kernels for gfx950 and the C ABI of include/vhx.h.
+// libvhx device side, trace unit: every kernel that traces rays, the pass scheduler and the trace entry points of
+// include/vhx.h.
 //
 // Kernels
-//   k_trace_primary  per-pixel primary rays (examples/gpu_render.rs:196-257, benches/performance.rs:29-66) traced with
-//                    get_by_ray semantics (src/raytracing/cpu.rs:296-458); replaces the WGSL `update` kernel dispatched
-//                    by VhxRenderNode::run (src/raytracing/bevy/pipeline/mod.rs:96-155)
-//   k_trace_rays     explicit ray batch (BoxTree::get_by_ray over many rays)
-//   k_brick_occ_*    upload-time brick occupancy bitmaps from pix_points_to_empty (src/boxtree/node.rs:311-333)
-//   k_pack_hdr       node type + occupied_bits -> one 16-byte record per node
-//   k_untile_rgba    scatters rank-gathered tile buffers into the framebuffer (multi-GPU screen-tile split)
+//   k_trace_primary, k_trace_primary_batch  pass 0 of a primary frame / a batch of frames: per-pixel primary rays
+//                    (examples/gpu_render.rs:196-257, benches/performance.rs:29-66) traced with get_by_ray semantics
+//                    (src/raytracing/cpu.rs:296-458); replaces the WGSL `update` kernel dispatched by
+//                    VhxRenderNode::run (src/raytracing/bevy/pipeline/mod.rs:96-155)
+//   k_trace_rays     pass 0 of an explicit ray batch (BoxTree::get_by_ray over many rays)
+//   k_trace_queue    the queue passes: the rays an earlier pass abandoned at its step budget, and shadow rays
+//   k_trace_tail, k_tail_mask  the early tail of a lone frame
+//   k_count_flags, k_emit_flags, k_scan_counts, k_scan_sums, k_gather_chunks, k_sort_segments  a pass's abandoned
+//                    rays (flags or chunk lists) compacted into the next pass's queue
+//   k_put_queue_args, k_chain (VHX_CHAIN builds)
+// The tree these kernels read is built by vhx_tree.hip; contexts, ordering and settings live in vhx_ctx.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,124 +26,9 @@
 #include "../../include/vhx.h"
 #include "trace.hpp"
 
-namespace vhx {
-__constant__ uint8_t c_step_lut[64 * 27];
-}
-
 using namespace vhx;
 
 #include "ctx.hpp"
-
-// SECTANT_STEP_RESULT_LUT generator (src/bin/sectant_step_result_lut.rs:48-114), host side
-static void make_step_lut(uint8_t *lut) {
-    for (int s = 0; s < 64; ++s)
-        for (int x = -1; x <= 1; ++x)
-            for (int y = -1; y <= 1; ++y)
-                for (int z = -1; z <= 1; ++z) {
-                    float off[3] = {(float)(s % 4) / 4.f, (float)((s / 4) % 4) / 4.f, (float)(s / 16) / 4.f};
-                    float st[3] = {(float)x, (float)y, (float)z};
-                    float after[3];
-                    bool out = false;
-                    for (int k = 0; k < 3; ++k) {
-                        after[k] = (off[k] + 0.25f / 2.f) + 0.25f * st[k];
-                        out |= after[k] < 0.f || after[k] > 1.f;
-                    }
-                    int base = 0;
-                    if (out) {
-                        for (int k = 0; k < 3; ++k) {
-                            after[k] = std::fmod(after[k], 1.f);
-                            if (after[k] < 0.f) after[k] += 1.f;
-                        }
-                        base = 64;
-                    }
-                    int ix = (int)std::floor(after[0] * 4.f), iy = (int)std::floor(after[1] * 4.f),
-                        iz = (int)std::floor(after[2] * 4.f);
-                    lut[s * 27 + (x + 1) * 9 + (y + 1) * 3 + (z + 1)] = (uint8_t)(base + ix + iy * 4 + iz * 16);
-                }
-}
-
-// ------------------------------------------------------------------------------------------------ upload kernels
-__device__ __forceinline__ bool cell_empty(uint32_t v, const uint32_t *color, uint32_t ncolor, const uint32_t *data,
-                                           uint32_t ndata) {
-    const uint32_t ci = v & 0xFFFFu, di = v >> 16;
-    const bool cn = ci == 0xFFFFu || ci >= ncolor || ((color[ci] >> 24) & 0xFFu) == 0;
-    const bool dn = di == 0xFFFFu || di >= ndata || data[di] == 0;
-    return cn && dn;
-}
-
-// bd^3 >= 64: one lane per cell, the wave's ballot is one 64-bit occupancy word
-__global__ void __launch_bounds__(256) k_brick_occ_ballot(const uint32_t *__restrict__ vox, uint64_t ncells,
-                                                          uint64_t cell0, const uint32_t *__restrict__ color,
-                                                          uint32_t ncolor, const uint32_t *__restrict__ data,
-                                                          uint32_t ndata, uint64_t *__restrict__ words) {
-    const uint64_t i = cell0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool in = i < cell0 + ncells;
-    const bool full = in && !cell_empty(vox[in ? i : cell0], color, ncolor, data, ndata);
-    const uint64_t m = __ballot(full);
-    if ((threadIdx.x & 63u) == 0 && in) words[i >> 6] = m;
-}
-
-// bd^3 < 64 (bd = 1, 2): one lane per brick
-__global__ void __launch_bounds__(256) k_brick_occ_small(const uint32_t *__restrict__ vox, uint32_t nbricks,
-                                                         uint32_t brick0, uint32_t n3,
-                                                         const uint32_t *__restrict__ color, uint32_t ncolor,
-                                                         const uint32_t *__restrict__ data, uint32_t ndata,
-                                                         uint64_t *__restrict__ words) {
-    const uint32_t b = brick0 + blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= brick0 + nbricks) return;
-    uint64_t m = 0;
-    for (uint32_t c = 0; c < n3; ++c)
-        if (!cell_empty(vox[(uint64_t)b * n3 + c], color, ncolor, data, ndata)) m |= 1ull << c;
-    words[b] = m;
-}
-
-// DevTree::child_rec for brick_dim <= 4: one record per child entry. Entries [e0, e1) are visited; with sel, only the
-// entries of nodes [node_lo, node_hi) and those holding a Parted brick in [brick_lo, brick_hi) are rewritten (a ranged
-// update: the records of written nodes and of the nodes whose bricks were written)
-struct RecSel {
-    uint32_t sel, node_lo, node_hi, brick_lo, brick_hi;
-};
-__global__ void __launch_bounds__(256) k_child_rec(const uint32_t *__restrict__ type,
-                                                   const uint32_t *__restrict__ children,
-                                                   const uint64_t *__restrict__ words, uint32_t brick_count,
-                                                   uint64_t e0, uint64_t e1, RecSel s, uint4 *__restrict__ rec) {
-    const uint64_t i = e0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= e1) return;
-    const uint32_t node = (uint32_t)(i >> 6);
-    const uint32_t ty = type[node];
-    const bool uniform = ty == VHX_NODE_UNIFORM_LEAF;
-    const uint32_t v = children[uniform ? (i & ~63ull) : i];
-    const bool parted = (uniform || ty == VHX_NODE_LEAF) && v != VHX_EMPTY && (v & VHX_SOLID_BIT) == 0 && v < brick_count;
-    if (s.sel && !(node >= s.node_lo && node < s.node_hi) && !(parted && v >= s.brick_lo && v < s.brick_hi)) return;
-    const uint64_t o = parted ? words[v] : 0ull;
-    rec[i] = make_uint4(v, (uint32_t)o, (uint32_t)(o >> 32), 0u);
-}
-
-// Ranged writes: job j copies `words` 32-bit words from the staging buffer at src_off to the device address dst (a
-// range cut into pieces of at most 16 KiB, one workgroup per piece)
-struct UpdJob {
-    uint64_t dst, src_off;
-    uint32_t words, pad0;
-    uint64_t pad1;
-};
-#define UPD_PIECE_BYTES 16384u
-__global__ void __launch_bounds__(256) k_scatter_ranges(const uint8_t *__restrict__ stage, uint32_t j0, uint32_t j1) {
-    const UpdJob *jobs = (const UpdJob *)stage;
-    for (uint32_t j = j0 + blockIdx.x; j < j1; j += gridDim.x) {
-        const UpdJob jb = jobs[j];
-        const uint32_t *src = (const uint32_t *)(stage + jb.src_off);
-        uint32_t *dst = (uint32_t *)jb.dst;
-        for (uint32_t w = threadIdx.x; w < jb.words; w += blockDim.x) dst[w] = src[w];
-    }
-}
-
-__global__ void __launch_bounds__(256) k_pack_hdr(const uint32_t *__restrict__ type, const uint64_t *__restrict__ occ,
-                                                  uint32_t n0, uint32_t n, uint4 *__restrict__ hdr) {
-    const uint32_t i = n0 + blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n0 + n) return;
-    const uint64_t o = occ[i];
-    hdr[i] = make_uint4((uint32_t)o, (uint32_t)(o >> 32), type[i], 0u);
-}
 
 // ------------------------------------------------------------------------------------------------ trace kernels
 struct CamD {
@@ -1317,31 +1207,6 @@ __global__ void __launch_bounds__(256) k_trace_tail(DevTree t, CamD cam, OutD ou
     if (h.iters >= tail_min) tail_record(next, cap, idx);
 }
 
-// Scatters rank-gathered tile buffers into framebuffers. Rank r's part of `gathered` holds `planes` planes of
-// tiles_per_rank*T*T words each (plane 0 RGBA8, plane 1 f32 depth bits), rank r traced tiles r, r + ranks, ...
-__global__ void __launch_bounds__(256) k_untile_planes(const uint32_t *__restrict__ gathered, uint32_t planes,
-                                                       uint32_t ranks, uint32_t tiles_per_rank, uint32_t T,
-                                                       uint32_t tiles_x, uint32_t ntiles, uint32_t width,
-                                                       uint32_t height, uint32_t *__restrict__ fb0,
-                                                       uint32_t *__restrict__ fb1) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t per_plane = (uint64_t)tiles_per_rank * T * T, per_rank = per_plane * planes;
-    if (i >= per_rank * ranks) return;
-    const uint32_t r = (uint32_t)(i / per_rank);
-    const uint64_t w = i - (uint64_t)r * per_rank;
-    const uint32_t plane = (uint32_t)(w / per_plane);
-    const uint64_t k = w - (uint64_t)plane * per_plane;
-    uint32_t *fb = plane ? fb1 : fb0;
-    if (!fb) return;
-    const uint32_t j = (uint32_t)(k / ((uint64_t)T * T));
-    const uint32_t local = (uint32_t)(k - (uint64_t)j * T * T);
-    const uint32_t tile = r + j * ranks;
-    if (tile >= ntiles) return;
-    const uint32_t px = (tile % tiles_x) * T + local % T, py = (tile / tiles_x) * T + local / T;
-    if (px >= width || py >= height) return;
-    fb[(uint64_t)py * width + px] = gathered[i];
-}
-
 // ------------------------------------------------------------------------------------------------ host helpers
 template <int V>
 struct BdTag {
@@ -1376,217 +1241,6 @@ static DevTree dev_tree(const vhx_ctx *c) {
     t.occ_words = c->tree->occ_words;
     t.mips = c->tree->mips_on ? (const uint32_t *)c->tree->mips.ptr : nullptr;
     return t;
-}
-
-TreeStore::~TreeStore() {
-    (void)hipSetDevice(device);
-    if (write_ev) (void)hipEventDestroy(write_ev);
-    for (auto &b : raw)
-        if (b.ptr) (void)hipFree(b.ptr);
-    for (DevBuf *b : {&hdr, &brick_occ, &child_rec, &mips})
-        if (b->ptr) (void)hipFree(b->ptr);
-}
-
-int vhx::ensure(vhx_ctx *c, DevBuf &b, uint64_t bytes) {
-    if (b.bytes >= bytes && b.ptr) return VHX_OK;
-    if (b.ptr) VHX_HIP(c, hipFree(b.ptr));
-    b.ptr = nullptr;
-    b.bytes = 0;
-    if (bytes == 0) bytes = 16;
-    VHX_HIP(c, hipMalloc(&b.ptr, bytes));
-    b.bytes = bytes;
-    return VHX_OK;
-}
-
-// ---- tree-write ordering (TreeStore): frames in flight on shared contexts and writes through the owner ----------
-// VHX_UNORDERED_WRITES=1 (a diagnostic build only, never the shipped library: voxelhex_amd._build.build(defines=
-// ("VHX_UNORDERED_WRITES=1",), lib=...)): no waits either way, the behaviour before round 3, to show that
-// tests/test_gpu_ordering.py detects the missing ordering
-#ifndef VHX_UNORDERED_WRITES
-#define VHX_UNORDERED_WRITES 0
-#endif
-static constexpr bool unordered_writes() { return VHX_UNORDERED_WRITES != 0; }
-
-// Writes and traces of one tree may come from several host threads (one per context): a write waits until no trace is
-// between trace_begin and trace_end (a trace in submission is not yet visible in its use event), and a trace waits
-// until no write is between write_begin and write_end, so every frame sees the tree as of its submission.
-int vhx::write_begin(vhx_ctx *c) {
-    TreeStore &ts = *c->tree;
-    std::unique_lock<std::mutex> lock(ts.mu);
-    // a waiting writer holds off traces that have not begun yet (trace_begin waits while writers_waiting > 0), so that
-    // a stream of back-to-back traces from other threads cannot keep `tracing` above 0 forever
-    ++ts.writers_waiting;
-    ts.cv.wait(lock, [&] { return ts.tracing == 0 && ts.writing == 0; });
-    --ts.writers_waiting;
-    ++ts.writing;
-    if (unordered_writes()) return VHX_OK;
-    // every other context's last submitted trace, whatever stream it went to (waiting on an event of c's own stream is
-    // a no-op, so no stream comparison: a context moved between streams by vhx_set_stream is still waited for)
-    for (vhx_ctx *u : ts.users)
-        if (u != c && u->use_recorded) VHX_HIP(c, hipStreamWaitEvent(c->stream, u->use_ev, 0));
-    // a write on another stream than the previous write also follows it (writes are ordered among themselves)
-    if (ts.write_seq && ts.write_stream != c->stream) VHX_HIP(c, hipStreamWaitEvent(c->stream, ts.write_ev, 0));
-    return VHX_OK;
-}
-
-int vhx::write_end(vhx_ctx *c) {
-    TreeStore &ts = *c->tree;
-    std::lock_guard<std::mutex> lock(ts.mu);
-    ts.writing = ts.writing > 0 ? ts.writing - 1 : 0;
-    ts.cv.notify_all();
-    // recorded on every exit (also after a failed write: the next traces wait for whatever it enqueued)
-    if (!ts.write_ev) VHX_HIP(c, hipEventCreateWithFlags(&ts.write_ev, hipEventDisableTiming));
-    VHX_HIP(c, hipEventRecord(ts.write_ev, c->stream));
-    ts.write_stream = c->stream;
-    ++ts.write_seq;
-    c->seen_write = ts.write_seq;
-    return VHX_OK;
-}
-
-int vhx::trace_begin(vhx_ctx *c) {
-    TreeStore &ts = *c->tree;
-    std::unique_lock<std::mutex> lock(ts.mu);
-    ts.cv.wait(lock, [&] { return ts.writing == 0 && ts.writers_waiting == 0; });
-    ++ts.tracing;
-    if (unordered_writes()) return VHX_OK;
-    if (c->seen_write != ts.write_seq) {
-        if (ts.write_stream != c->stream) VHX_HIP(c, hipStreamWaitEvent(c->stream, ts.write_ev, 0));
-        c->seen_write = ts.write_seq;
-    }
-    return VHX_OK;
-}
-
-int vhx::trace_end(vhx_ctx *c) {
-    TreeStore &ts = *c->tree;
-    std::lock_guard<std::mutex> lock(ts.mu);  // write_begin reads use_recorded / waits on use_ev
-    ts.tracing = ts.tracing > 0 ? ts.tracing - 1 : 0;
-    ts.cv.notify_all();
-    if (!c->use_ev) VHX_HIP(c, hipEventCreateWithFlags(&c->use_ev, hipEventDisableTiming));
-    VHX_HIP(c, hipEventRecord(c->use_ev, c->stream));
-    c->use_stream = c->stream;
-    c->use_recorded = true;
-    return VHX_OK;
-}
-
-static void register_user(vhx_ctx *c) {
-    std::lock_guard<std::mutex> lock(c->tree->mu);
-    c->tree->users.push_back(c);
-    c->seen_write = 0;  // the first trace waits for the tree's last write (if any, and on another stream)
-}
-
-static void unregister_user(vhx_ctx *c) {
-    std::lock_guard<std::mutex> lock(c->tree->mu);
-    auto &u = c->tree->users;
-    u.erase(std::remove(u.begin(), u.end(), c), u.end());
-}
-
-void vhx::pack_counts(const vhx_tree_desc &d, uint32_t counts[8]) {
-    const uint32_t v[8] = {d.boxtree_size, d.brick_dim, d.node_count, d.brick_count,
-                           d.solid_count, d.color_count, d.data_count, 0};
-    std::memcpy(counts, v, sizeof(v));
-}
-
-vhx_tree_desc vhx::unpack_counts(const uint32_t counts[8]) {
-    vhx_tree_desc d{};
-    d.boxtree_size = counts[0];
-    d.brick_dim = counts[1];
-    d.node_count = counts[2];
-    d.brick_count = counts[3];
-    d.solid_count = counts[4];
-    d.color_count = counts[5];
-    d.data_count = counts[6];
-    return d;
-}
-
-uint64_t vhx::elem_size(int id) {
-    switch (id) {
-        case VHX_BUF_NODE_OCBITS: return 8;
-        default: return 4;
-    }
-}
-uint64_t vhx::elem_count(const vhx_tree_desc &d, int id) {
-    const uint64_t n3 = (uint64_t)d.brick_dim * d.brick_dim * d.brick_dim;
-    switch (id) {
-        case VHX_BUF_NODE_TYPE: return d.node_count;
-        case VHX_BUF_NODE_OCBITS: return d.node_count;
-        case VHX_BUF_NODE_CHILDREN: return (uint64_t)d.node_count * 64;
-        case VHX_BUF_VOXELS: return (uint64_t)d.brick_count * n3;
-        case VHX_BUF_SOLID_VALUES: return d.solid_count;
-        case VHX_BUF_COLOR_PALETTE: return d.color_count;
-        case VHX_BUF_DATA_PALETTE: return d.data_count;
-    }
-    return 0;
-}
-
-static int rebuild_hdr(vhx_ctx *c, uint32_t n0, uint32_t n) {
-    if (n == 0) return VHX_OK;
-    k_pack_hdr<<<(n + 255) / 256, 256, 0, c->stream>>>((const uint32_t *)c->tree->raw[VHX_BUF_NODE_TYPE].ptr,
-                                                       (const uint64_t *)c->tree->raw[VHX_BUF_NODE_OCBITS].ptr, n0, n,
-                                                       (uint4 *)c->tree->hdr.ptr);
-    VHX_HIP(c, hipGetLastError());
-    return VHX_OK;
-}
-
-static bool has_child_rec(const vhx_ctx *c) {
-    const uint32_t bd = c->tree->desc.brick_dim;
-    return bd * bd * bd <= 64;
-}
-
-// DevTree::child_rec depends on node types, children and brick occupancy: updates mark it stale and the next trace
-// rebuilds it whole (one pass over the child entries, ~n_nodes * 64 * 24 bytes)
-static int refresh_child_rec(vhx_ctx *c) {
-    if (!has_child_rec(c) || !c->tree->child_rec_stale) return VHX_OK;
-    const uint64_t n = (uint64_t)c->tree->desc.node_count * 64;
-    k_child_rec<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(
-        (const uint32_t *)c->tree->raw[VHX_BUF_NODE_TYPE].ptr, (const uint32_t *)c->tree->raw[VHX_BUF_NODE_CHILDREN].ptr,
-        (const uint64_t *)c->tree->brick_occ.ptr, c->tree->desc.brick_count, 0, n, RecSel{0, 0, 0, 0, 0},
-        (uint4 *)c->tree->child_rec.ptr);
-    VHX_HIP(c, hipGetLastError());
-    c->tree->child_rec_stale = false;
-    return VHX_OK;
-}
-
-// The child records of nodes [node_lo, node_hi) and of the nodes holding Parted bricks [brick_lo, brick_hi) (either
-// range may be empty): a pass over the written nodes' entries, or over every child entry when bricks were written (the
-// brick -> holder relation lives only in the children array; reading it is 256 B per node, the records are 1 KB).
-static int refresh_child_rec_sel(vhx_ctx *c, uint32_t node_lo, uint32_t node_hi, uint32_t brick_lo, uint32_t brick_hi) {
-    if (!has_child_rec(c) || c->tree->child_rec_stale) return VHX_OK;  // a stale buffer is rebuilt whole anyway
-    const bool bricks = brick_lo < brick_hi, nodes = node_lo < node_hi;
-    if (!bricks && !nodes) return VHX_OK;
-    const uint64_t e0 = bricks ? 0 : (uint64_t)node_lo * 64, e1 = bricks ? (uint64_t)c->tree->desc.node_count * 64
-                                                                           : (uint64_t)node_hi * 64;
-    k_child_rec<<<(unsigned)((e1 - e0 + 255) / 256), 256, 0, c->stream>>>(
-        (const uint32_t *)c->tree->raw[VHX_BUF_NODE_TYPE].ptr, (const uint32_t *)c->tree->raw[VHX_BUF_NODE_CHILDREN].ptr,
-        (const uint64_t *)c->tree->brick_occ.ptr, c->tree->desc.brick_count, e0, e1,
-        RecSel{1, node_lo, node_hi, brick_lo, brick_hi}, (uint4 *)c->tree->child_rec.ptr);
-    VHX_HIP(c, hipGetLastError());
-    return VHX_OK;
-}
-
-static int rebuild_occ(vhx_ctx *c, uint32_t brick0, uint32_t nbricks) {
-    if (nbricks == 0) return VHX_OK;
-    const uint32_t bd = c->tree->desc.brick_dim;
-    const uint32_t n3 = bd * bd * bd;
-    const uint32_t *vox = (const uint32_t *)c->tree->raw[VHX_BUF_VOXELS].ptr;
-    const uint32_t *col = (const uint32_t *)c->tree->raw[VHX_BUF_COLOR_PALETTE].ptr;
-    const uint32_t *dat = (const uint32_t *)c->tree->raw[VHX_BUF_DATA_PALETTE].ptr;
-    if (n3 >= 64) {
-        const uint64_t cell0 = (uint64_t)brick0 * n3, ncells = (uint64_t)nbricks * n3;
-        // grid-stride chunks keep gridDim.x within range for multi-GB voxel buffers
-        const uint64_t chunk = 1ull << 30;
-        for (uint64_t s = 0; s < ncells; s += chunk) {
-            const uint64_t n = std::min(chunk, ncells - s);
-            k_brick_occ_ballot<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(
-                vox, n, cell0 + s, col, c->tree->desc.color_count, dat, c->tree->desc.data_count, (uint64_t *)c->tree->brick_occ.ptr);
-            VHX_HIP(c, hipGetLastError());
-        }
-    } else {
-        k_brick_occ_small<<<(nbricks + 255) / 256, 256, 0, c->stream>>>(vox, nbricks, brick0, n3, col,
-                                                                         c->tree->desc.color_count, dat, c->tree->desc.data_count,
-                                                                         (uint64_t *)c->tree->brick_occ.ptr);
-        VHX_HIP(c, hipGetLastError());
-    }
-    return VHX_OK;
 }
 
 struct HostOut {
@@ -1884,54 +1538,82 @@ static int put_qargs(vhx_ctx *c, const CamD &cam, const RaySrc &src, const OutD 
     return VHX_OK;
 }
 
+// How a grid pass 0 hands its abandoned rays to the queue passes (launch_queue_passes)
+enum { P0_LISTS = 0, P0_FLAGS = 1, P0_ORDERED = 2 };
+
+// Flags -> queue: the set flags of `npos` positions in the order `ord` (HITS false: pass 0's flag byte per output
+// index; HITS true: a hit value != VHX_EMPTY, the hit pixels a shadow pass starts from) listed at `out`, their number at
+// *total. The count kernel also zeroes the queue passes' work counters and, when given, the nclear entries of `clear`.
+template <bool HITS>
+static int compact_flags(vhx_ctx *c, const void *src, uint64_t npos, const FlagOrder &ord, uint32_t *total,
+                         uint32_t *out, uint32_t *clear = nullptr, uint64_t nclear = 0) {
+    const unsigned nb = (unsigned)((npos + 1023) / 1024);
+    // a shadow batch in a tile order scans more positions than prepare_passes sized the chunk counts for
+    if ((uint64_t)nb * 4 > c->counts.bytes || (uint64_t)nb * 4 > c->offsets.bytes) {
+        const int rc = ensure_lists(c, nb);
+        if (rc) return rc;
+    }
+    uint32_t *counts = (uint32_t *)c->counts.ptr, *offsets = (uint32_t *)c->offsets.ptr;
+    k_count_flags<HITS><<<nb, 256, 0, c->stream>>>(src, npos, counts, (uint32_t *)c->qctl.ptr + 16, clear, ord, nclear);
+    launch_scan(c, counts, nb, nullptr, 1, offsets, total, nb);
+    k_emit_flags<HITS><<<nb, 256, 0, c->stream>>>(src, npos, offsets, out, ord);
+    VHX_HIP(c, hipGetLastError());
+    debug_passes(c, "compacted flags");
+    return VHX_OK;
+}
+
+// A trace's queue passes (launch_queue_passes): what they trace, and how pass 0 handed over its abandoned rays
+struct QueueRun {
+    CamD cam{};
+    RaySrc src{};
+    OutD out{};
+    uint32_t first = 1;  // the first queue pass: 1 after a grid pass 0, 0 where pass 0 is itself a queue pass
+    uint32_t npass = 1;
+    uint64_t nout = 0;      // rays of the trace
+    uint64_t nblocks0 = 0;  // workgroups of the grid pass 0
+    int pass0 = P0_LISTS;
+    uint32_t order_w = 0, order_h = 0;  // P0_FLAGS: the frame in whose queue order (c->qorder) the flags are compacted
+    uint32_t frames = 1;                // frames of a batch
+    bool qm = false;                    // queue-state mode (queue_state_mode)
+};
+
 // Queue passes first..npass-1: pass p re-traces the queue of pass p-1 (pass 0's queue, for first == 0, is the list
 // in queue[1] with its length in qctl[7]); what exceeds its budget is listed per chunk and compacted into the next
 // pass's queue. For first == 1, pass 0 (a grid kernel of nblocks0 workgroups) has just run and is compacted first:
 // its per-workgroup lists (P0_LISTS, in workgroup order; P0_ORDERED, already in the queue order, ListOrder), or its
 // per-ray flags in the queue order (P0_FLAGS).
-enum { P0_LISTS = 0, P0_FLAGS = 1, P0_ORDERED = 2 };
 template <bool COUNT, int BD, bool MIP = false, bool FUSE = false>
-static int launch_queue_passes(vhx_ctx *c, const DevTree &t, const CamD &cam, const RaySrc &src, const OutD &o,
-                               uint32_t first, uint32_t npass, uint64_t nout, uint64_t nblocks0,
-                               int pass0 = P0_LISTS, uint32_t order_w = 0, uint32_t order_h = 0,
-                               uint32_t frames = 1, bool qm = false) {
-    uint32_t *ctl = (uint32_t *)c->qctl.ptr;
+static int launch_queue_passes(vhx_ctx *c, const DevTree &t, const QueueRun &r) {
+    const uint32_t npass = r.npass;
+    uint32_t *ctl = (uint32_t *)c->qctl.ptr, *queue0 = (uint32_t *)c->queue[0].ptr;
     int rc = VHX_OK;
-    if (first > 0 && npass > 1) {
-        if (pass0 == P0_FLAGS) {  // primary frames: per-ray flags compacted in output-index (frame) order
+    if (r.first > 0 && npass > 1) {
+        if (r.pass0 == P0_FLAGS) {  // primary frames: per-ray flags compacted in output-index (frame) order
             // tile order (c->qorder, framebuffer layout only): positions over the frame's tiles
-            uint64_t npos = nout;
-            const FlagOrder ord = flag_order(c->qorder, order_w, order_h, npos, frames);
-            const unsigned nb = (unsigned)((npos + 1023) / 1024);
-            uint32_t *counts = (uint32_t *)c->counts.ptr, *offsets = (uint32_t *)c->offsets.ptr;
-            const uint8_t *flags = (const uint8_t *)c->flags.ptr;
-            k_count_flags<false><<<nb, 256, 0, c->stream>>>(flags, npos, counts, ctl + 16, nullptr, ord);
-            launch_scan(c, counts, nb, nullptr, 1, offsets, ctl, nb);
-            k_emit_flags<false><<<nb, 256, 0, c->stream>>>(flags, npos, offsets, (uint32_t *)c->queue[0].ptr, ord);
-            VHX_HIP(c, hipGetLastError());
-            debug_passes(c, "compacted flags");
-            if ((rc = sort_segments(c, 1, npass, (uint32_t *)c->queue[0].ptr, ctl, nout))) return rc;
-        } else if (pass0 == P0_ORDERED) {  // per-wave lists (wave_append): 4 chunks of 64 per workgroup
-            rc = compact_chunks(c, (uint32_t)(nblocks0 * 4), nullptr, 64, 64, (uint32_t *)c->queue[0].ptr, ctl,
-                                nblocks0 * 4, qm);
-            if (!rc) rc = sort_segments(c, 1, npass, (uint32_t *)c->queue[0].ptr, ctl, nout);
+            uint64_t npos = r.nout;
+            const FlagOrder ord = flag_order(c->qorder, r.order_w, r.order_h, npos, r.frames);
+            if ((rc = compact_flags<false>(c, c->flags.ptr, npos, ord, ctl, queue0))) return rc;
+            if ((rc = sort_segments(c, 1, npass, queue0, ctl, r.nout))) return rc;
+        } else if (r.pass0 == P0_ORDERED) {  // per-wave lists (wave_append): 4 chunks of 64 per workgroup
+            rc = compact_chunks(c, (uint32_t)(r.nblocks0 * 4), nullptr, 64, 64, queue0, ctl, r.nblocks0 * 4, r.qm);
+            if (!rc) rc = sort_segments(c, 1, npass, queue0, ctl, r.nout);
         } else {
-            rc = compact_chunks(c, (uint32_t)nblocks0, nullptr, 256, 256, (uint32_t *)c->queue[0].ptr, ctl, nblocks0);
+            rc = compact_chunks(c, (uint32_t)r.nblocks0, nullptr, 256, 256, queue0, ctl, r.nblocks0);
         }
     }
     QueueArgs *qa = nullptr;
-    if (first < npass && (rc = put_qargs(c, cam, src, o, qa))) return rc;
-    for (uint32_t p = first; p < npass && !rc; ++p) {
+    if (r.first < npass && (rc = put_qargs(c, r.cam, r.src, r.out, qa))) return rc;
+    for (uint32_t p = r.first; p < npass && !rc; ++p) {
         const uint32_t *in = (const uint32_t *)c->queue[(p - 1) & 1u].ptr;  // p = 0: queue[1]
         const uint32_t *in_n = p > 0 ? ctl + (p - 1) : ctl + 7;
-        const PassQ q = pass_q(c, p, npass, qm);
+        const PassQ q = pass_q(c, p, npass, r.qm);
         // a first pass over fresh rays (the shadow path) is throughput-bound like a grid launch: more waves
         uint32_t qwaves = p == 0 ? c->queue_waves0
                           : (p + 1 < npass && c->queue_waves_mid ? c->queue_waves_mid : c->queue_waves);
         // a batch of frames: the waves the same frames would bring as frames in flight (one frame's queue waves each),
         // up to the queue kernel's residency (5 waves per SIMD): its queue passes are memory-latency bound and need
         // the waves in flight
-        if (frames > 1 && p > 0) qwaves = (uint32_t)std::min<uint64_t>((uint64_t)qwaves * frames, 20ull * c->cus);
+        if (r.frames > 1 && p > 0) qwaves = (uint32_t)std::min<uint64_t>((uint64_t)qwaves * r.frames, 20ull * c->cus);
         const unsigned qgrid = (qwaves * 64u + c->qblock - 1) / c->qblock;
         uint32_t *grab = ctl + 16u + QCTL_PASS_WORDS * p;
         if constexpr (!FUSE && !MIP) {  // (the queue-state mode excludes fused shadows; MIP frames never list pass 0)
@@ -1945,123 +1627,268 @@ static int launch_queue_passes(vhx_ctx *c, const DevTree &t, const CamD &cam, co
         debug_passes(c, "queue pass");
         if (p + 1 < npass) {
             rc = compact_chunks(c, 0, in_n, q.rpw, q.rpw, (uint32_t *)c->queue[p & 1u].ptr, ctl + p,
-                                q.rpw ? (nout + q.rpw - 1) / q.rpw : nout, qm);
-            if (!rc) rc = sort_segments(c, p + 1, npass, (uint32_t *)c->queue[p & 1u].ptr, ctl + p, nout);
+                                q.rpw ? (r.nout + q.rpw - 1) / q.rpw : r.nout, r.qm);
+            if (!rc) rc = sort_segments(c, p + 1, npass, (uint32_t *)c->queue[p & 1u].ptr, ctl + p, r.nout);
         }
     }
     return rc;
 }
 
+// The kernel variants that exist besides brick_dim: MIP stand-ins, byte counting, fused shadows, the depth prepass's
+// start (FAST, pass 0 of a primary frame only), or none of them -- never two at once, which the entry points refuse.
+// f(BdTag, VarTag) is instantiated for these five tags only, so no other combination of a kernel is built.
+template <bool C, bool M, bool F, bool S>
+struct VarTag {
+    static constexpr bool COUNT = C, MIP = M, FUSE = F, FAST = S;
+};
+template <class Fn>
+static bool dispatch_variant(uint32_t bd, bool mip, bool count, bool fuse, bool fast, Fn &&f) {
+    return dispatch_bd(bd, [&](auto b) {
+        if (mip) f(b, VarTag<false, true, false, false>{});
+        else if (count) f(b, VarTag<true, false, false, false>{});
+        else if (fuse) f(b, VarTag<false, false, true, false>{});
+        else if (fast) f(b, VarTag<false, false, false, true>{});
+        else f(b, VarTag<false, false, false, false>{});
+    });
+}
+
+// ------------------------------------------------------------------------------------------ trace entry points
+// What every trace entry point does around its launches. The constructor selects the device and the context's stream
+// and opens the trace's scope in the tree-write ordering: the trace follows the tree's last write (an update through the
+// owner, on its stream). nested: the depth prepass's inner frame, which runs inside its outer frame's scope and time.
+// rc != 0 after construction: the entry point returns it.
+struct TraceCall {
+    vhx_ctx *c;
+    const bool nested;
+    int rc;
+    TraceScope scope;
+    explicit TraceCall(vhx_ctx *ctx, bool nested_ = false)
+        : c(ctx), nested(nested_), rc(use_stream(ctx)), scope(ctx, nested_ || rc != VHX_OK) {
+        if (!rc) rc = scope.rc;
+    }
+    static int use_stream(vhx_ctx *c) {
+        VHX_HIP(c, hipSetDevice(c->device));
+        VHX_STREAM(c);
+        return VHX_OK;
+    }
+    // the tree as the kernels read it, its child records rebuilt first where an update left them stale
+    int tree(DevTree &t) {
+        const int r = refresh_child_rec(c);
+        if (!r) t = dev_tree(c);
+        return r;
+    }
+    // the start of the time vhx_sync reports; a shadow trace that completes a frame (keep_ev0) keeps the start of the
+    // frame's primary trace
+    int start() {
+        if (!nested && !c->keep_ev0) VHX_HIP(c, hipEventRecord(c->ev0, c->stream));
+        return VHX_OK;
+    }
+    // after the last launch (qrc: what the launches returned): the end of the timed region and of the scope -- a later
+    // write of the tree waits for this trace
+    int end(int qrc) {
+        if (qrc) return qrc;
+        VHX_HIP(c, hipGetLastError());
+        if (nested) return VHX_OK;  // the outer call records the end
+        VHX_HIP(c, hipEventRecord(c->ev1, c->stream));
+        c->timed = true;
+        return scope.end();
+    }
+};
+
+// Whether a written range meets a read range (1) or another written range (2), else 0; null and empty ranges meet
+// nothing. With both kinds present, the kind of the first written range, in the caller's order, that meets anything.
+struct MemRange {
+    const void *p;
+    uint64_t bytes;
+};
+static int ranges_meet(const std::vector<MemRange> &written, const std::vector<MemRange> &read) {
+    struct E {
+        const char *p, *end;
+        bool w;
+    };
+    std::vector<E> es;
+    for (const MemRange &r : written)
+        if (r.p && r.bytes) es.push_back({(const char *)r.p, (const char *)r.p + r.bytes, true});
+    for (const MemRange &r : read)
+        if (r.p && r.bytes) es.push_back({(const char *)r.p, (const char *)r.p + r.bytes, false});
+    // in address order, a range that starts before the end of an earlier one meets it (two read ranges may)
+    std::sort(es.begin(), es.end(), [](const E &a, const E &b) { return a.p < b.p; });
+    const char *wend = nullptr, *rend = nullptr;
+    bool any = false;
+    for (const E &e : es) {
+        if (e.p < wend || (e.w && e.p < rend)) any = true;
+        const char *&end = e.w ? wend : rend;
+        end = std::max(end, e.end);
+    }
+    if (!any) return 0;
+    auto meet = [](const MemRange &a, const MemRange &b) {
+        return a.p && b.p && a.bytes && b.bytes && (const char *)a.p < (const char *)b.p + b.bytes &&
+               (const char *)b.p < (const char *)a.p + a.bytes;
+    };
+    for (size_t i = 0; i < written.size(); ++i) {
+        for (const MemRange &r : read)
+            if (meet(written[i], r)) return 1;
+        for (size_t j = i + 1; j < written.size(); ++j)
+            if (meet(written[i], written[j])) return 2;
+    }
+    return 0;
+}
+
+// Staged batch arguments (a batch's cameras and outputs, a shadow batch's frame records): the next slot of a pinned
+// staging ring, sized for `bytes`, and the device buffer it is copied to. The host waits only if that slot's previous
+// copy (VHX_STAGE_SLOTS batches ago on this context) has not run yet. The caller fills P->ptr, then stage_commit.
+static int stage_acquire(vhx_ctx *c, vhx_ctx::Pinned *ring, uint32_t &next, DevBuf &dev, uint64_t bytes,
+                         vhx_ctx::Pinned *&out) {
+    vhx_ctx::Pinned &P = ring[next];
+    next = (next + 1) % std::max<uint32_t>(1u, std::min(c->stage_slots, vhx_ctx::VHX_STAGE_SLOTS));
+    if (P.used) VHX_HIP(c, hipEventSynchronize(P.done));
+    if (P.bytes < bytes) {
+        if (P.ptr) VHX_HIP(c, hipHostFree(P.ptr));
+        P.ptr = nullptr;
+        P.bytes = 0;
+        VHX_HIP(c, hipHostMalloc(&P.ptr, bytes, hipHostMallocDefault));
+        P.bytes = bytes;
+    }
+    if (!P.done) VHX_HIP(c, hipEventCreateWithFlags(&P.done, hipEventDisableTiming));
+    out = &P;
+    // the device copy is read by this context's earlier batches: a stream change waits for them
+    if (c->use_recorded && c->use_stream != c->stream) VHX_HIP(c, hipStreamWaitEvent(c->stream, c->use_ev, 0));
+    return ensure(c, dev, bytes);
+}
+// one copy to the device ahead of the launches on the context's stream (back-to-back batches on one context do not
+// wait on the host until the ring wraps onto a copy that has not run)
+static int stage_commit(vhx_ctx *c, vhx_ctx::Pinned &P, const DevBuf &dev, uint64_t bytes) {
+    VHX_HIP(c, hipMemcpyAsync(dev.ptr, P.ptr, bytes, hipMemcpyHostToDevice, c->stream));
+    VHX_HIP(c, hipEventRecord(P.done, c->stream));
+    P.used = true;
+    return VHX_OK;
+}
+
+// How pass 0 of a primary frame, or of a batch of them, hands its abandoned rays to the queue passes
+struct Pass0Plan {
+    bool listed = false;  // pass 0 lists them per wave, in the queue order (lo); else it writes a flag per ray
+    ListOrder lo{};
+    uint64_t nbf = 0;     // pass-0 workgroups per frame: over whole tiles of the list order when listed by it
+    bool qm = false;      // the trace runs in the queue-state mode
+    bool fuse = false;    // its shadow rays are fused into the ladder
+    int p0() const { return listed ? P0_ORDERED : P0_FLAGS; }
+};
+// fb_lists: whole W x H framebuffer frames in 16x16 blocks, which pass 0 can list in the default queue order itself
+// (ListOrder). tile_lists: tile sets, listed in their own block order (ListOrder::tl) -- no flag per entry, no
+// compaction over every entry, and the queue-state mode. nbf: a frame's pass-0 workgroups; shadows: a shadow light is
+// in force. Lists of more than 2^31 chunks: refused (refuse_oversize) or replaced by flags.
+static int plan_pass0(vhx_ctx *c, uint32_t npass, bool fb_lists, bool tile_lists, uint32_t W, uint32_t H, uint64_t nbf,
+                      uint32_t frames, bool shadows, bool refuse_oversize, Pass0Plan &p) {
+    const bool lists = c->p0lists && npass > 1;
+    const auto unlisted = [&] {
+        p = Pass0Plan{};
+        p.nbf = nbf;
+    };
+    unlisted();
+    if (lists && fb_lists && list_order(c->qorder, W, H, p.lo, p.nbf)) p.listed = true;
+    else unlisted();
+    if (!p.listed && lists && tile_lists && c->tile_lists) {
+        p.listed = true;
+        p.lo.tl = 1;
+    }
+    const bool oversize = p.nbf * frames * 4 > 0x7FFFFFFFull;  // four chunk counts per workgroup
+    if (p.listed && oversize && !refuse_oversize) unlisted();
+    int rc = VHX_OK;
+    if (p.listed && (rc = ensure_lists(c, p.nbf * frames))) return rc;
+    if (p.listed && oversize) return fail(c, VHX_E_INVALID_ARG, "frame too large");
+    p.qm = queue_state_mode(c, p.listed, false, npass);
+    // shadows fuse into the ladder where pass 0 lists its rays (the list entries carry the shadow tag); a single pass
+    // or the lone frame's flag compaction traces them after the primary rays instead
+    p.fuse = shadows && p.listed && npass > 1;
+    return VHX_OK;
+}
+
+// Pass 0's PassQ. A pass that lists its rays in the queue order zeroes the queue passes' counters itself (no flag
+// compaction follows it to do so); one compacted from flags writes them; a ray batch's block lists (P0_LISTS) need neither.
+static PassQ pass0_q(const vhx_ctx *c, uint32_t npass, int p0, bool qm = false) {
+    PassQ q = pass_q(c, 0, npass, qm);
+    if (p0 == P0_ORDERED)
+        q.zero = (uint32_t *)c->qctl.ptr + 16;
+    else if (p0 == P0_FLAGS && npass > 1)
+        q.flags = (uint8_t *)c->flags.ptr;
+    return q;
+}
+
+// The depth prepass of a frame (vhx_set_depth_prepass): its half-resolution camera ...
+static vhx_camera half_camera(const vhx_camera *cam) {
+    vhx_camera hc = *cam;
+    hc.width = (cam->width + 1) / 2;
+    hc.height = (cam->height + 1) / 2;
+    if (cam->ray_model == VHX_RAY_GLASS) {
+        // texel (X, Y) looks through the centre of full pixels 2X..2X+1, 2Y..2Y+1 (y counted upward in the glass)
+        const float ox = 0.5f * cam->pixel_width, oy = ((float)cam->height + 0.5f - 2.0f * (float)hc.height) * cam->pixel_height;
+        for (int k = 0; k < 3; ++k)
+            hc.glass_bottom_left[k] = cam->glass_bottom_left[k] + cam->glass_right[k] * ox + cam->glass_up[k] * oy;
+        hc.pixel_width = 2.0f * cam->pixel_width;
+        hc.pixel_height = 2.0f * cam->pixel_height;
+    }
+    return hc;
+}
+// ... and its half-resolution depth frame, traced by a nested call on the same stream; the full frame starts from it
+static int trace_prepass(vhx_ctx *c, const vhx_camera *cam, FastD &fd) {
+    const vhx_camera hc = half_camera(cam);
+    int rc = ensure(c, c->prepass_depth, (uint64_t)hc.width * hc.height * 4);
+    if (rc) return rc;
+    vhx_hits dh{};
+    dh.depth = (float *)c->prepass_depth.ptr;
+    c->in_prepass = true;
+    rc = vhx_trace_primary(c, &hc, 0, 0, 1, VHX_LAYOUT_FRAMEBUFFER, &dh, 1);
+    c->in_prepass = false;
+    if (rc) return rc;
+    fd = FastD{(const float *)c->prepass_depth.ptr, hc.width, hc.height, c->prepass_margin};
+    return VHX_OK;
+}
+
+// Early tail (vhx_ctx::tail_*), set-up: the lists, the mask and the second stream; the list this frame records
+// (c->tail_rec) is cleared; `use`: this context's last lone frame of the same size recorded a list, whose pixels the
+// early tail traces on the second stream (forked here) while pass 0 skips them (tail_mask)
+static int tail_begin(vhx_ctx *c, uint32_t W, uint32_t H, uint64_t nout, bool &use) {
+    const uint64_t lbytes = (64ull + c->tail_cap) * 4ull, mbytes = ((nout + 31) / 32) * 4;
+    int rc;
+    if ((rc = ensure(c, c->tail_list[0], lbytes)) || (rc = ensure(c, c->tail_list[1], lbytes)) ||
+        (rc = ensure(c, c->tail_mask, mbytes)))
+        return rc;
+    if (!c->tail_stream) {
+        int least = 0, greatest = 0;
+        VHX_HIP(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
+        VHX_HIP(c, hipStreamCreateWithPriority(&c->tail_stream, hipStreamNonBlocking, greatest));
+        VHX_HIP(c, hipEventCreateWithFlags(&c->tail_fork, hipEventDisableTiming));
+        VHX_HIP(c, hipEventCreateWithFlags(&c->tail_join, hipEventDisableTiming));
+    }
+    uint32_t *next = (uint32_t *)c->tail_list[c->tail_cur ^ 1u].ptr;
+    VHX_HIP(c, hipMemsetAsync(next, 0, 4, c->stream));
+    use = c->tail_valid && c->tail_w == W && c->tail_h == H;
+    if (use) {
+        VHX_HIP(c, hipMemsetAsync(c->tail_mask.ptr, 0, mbytes, c->stream));
+        k_tail_mask<<<16, 256, 0, c->stream>>>((const uint32_t *)c->tail_list[c->tail_cur].ptr, c->tail_cap,
+                                               (uint32_t)nout, (uint32_t *)c->tail_mask.ptr);
+        VHX_HIP(c, hipEventRecord(c->tail_fork, c->stream));
+        VHX_HIP(c, hipStreamWaitEvent(c->tail_stream, c->tail_fork, 0));
+    }
+    c->tail_rec = next;
+    return VHX_OK;
+}
+// ... and end: the frame ends with its early tail (joined before ev1 and the trace's use event); its record is the next
+// frame's list (the list it traced stays valid: an error later still leaves two well-formed lists)
+static int tail_end(vhx_ctx *c, uint32_t W, uint32_t H, bool use) {
+    if (use) {
+        VHX_HIP(c, hipEventRecord(c->tail_join, c->tail_stream));
+        VHX_HIP(c, hipStreamWaitEvent(c->stream, c->tail_join, 0));
+    }
+    c->tail_cur ^= 1u;
+    c->tail_valid = true;
+    c->tail_w = W;
+    c->tail_h = H;
+    return VHX_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
-
-uint32_t vhx_abi_version(void) { return VHX_ABI_VERSION; }
-
-// The HIP runtime's answer, with its error: hipGetDeviceCount failing for any reason other than "no device" is
-// VHX_E_HIP (count 0) and its text is kept for vhx_device_error (there is no context to hold it), instead of a silent
-// count of 0 (a process that lost the device must say why)
-static thread_local std::string g_device_err;
-int vhx_device_count(int *count) {
-    if (!count) return VHX_E_INVALID_ARG;
-    int n = 0;
-    const hipError_t e = hipGetDeviceCount(&n);
-    if (e == hipErrorNoDevice) n = 0;  // no GPU visible: a count of 0, not an error (a CPU-only host)
-    else if (e != hipSuccess) {
-        g_device_err = std::string("hipGetDeviceCount: ") + hipGetErrorName(e) + ": " + hipGetErrorString(e);
-        *count = 0;
-        return VHX_E_HIP;
-    }
-    g_device_err.clear();
-    *count = n;
-    return VHX_OK;
-}
-
-const char *vhx_device_error(void) { return g_device_err.c_str(); }
-
-int vhx_create(int hip_device, vhx_ctx **out) {
-    if (!out) return VHX_E_INVALID_ARG;
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return VHX_E_NO_DEVICE;
-    if (hip_device < 0 || hip_device >= n) return VHX_E_INVALID_ARG;
-    vhx_ctx *c = new vhx_ctx();
-    c->device = hip_device;
-    c->tree = std::make_shared<TreeStore>();
-    c->tree->device = hip_device;
-    register_user(c);
-    auto bail = [&](const char *what, hipError_t e) {
-        fprintf(stderr, "vhx_create: %s: %s\n", what, hipGetErrorString(e));
-        delete c;
-        return VHX_E_HIP;
-    };
-    hipError_t e;
-    if ((e = hipSetDevice(hip_device)) != hipSuccess) return bail("hipSetDevice", e);
-    // no stream yet: the caller's (vhx_set_stream) or the context's own, created at first use (VHX_STREAM). The
-    // library reads no environment: the schedule is the adaptive default until vhx_set_pass_budgets / vhx_set_tuning.
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, hip_device) == hipSuccess && prop.multiProcessorCount > 0) {
-            c->cus = (uint32_t)prop.multiProcessorCount;
-            c->queue_blocks = c->cus * 8u;
-            c->queue_waves = c->sched_busy.queue_waves_per_cu * c->cus;
-        }
-    }
-    if ((e = hipEventCreate(&c->ev0)) != hipSuccess) return bail("hipEventCreate", e);
-    if ((e = hipEventCreate(&c->ev1)) != hipSuccess) return bail("hipEventCreate", e);
-
-    uint8_t lut[64 * 27];
-    make_step_lut(lut);
-    if ((e = hipMemcpyToSymbol(HIP_SYMBOL(vhx::c_step_lut), lut, sizeof(lut))) != hipSuccess)
-        return bail("hipMemcpyToSymbol", e);
-    *out = c;
-    return VHX_OK;
-}
-
-int vhx_create_shared(const vhx_ctx *owner, vhx_ctx **out) {
-    if (!owner || !out) return VHX_E_INVALID_ARG;
-    *out = nullptr;
-    vhx_ctx *c = nullptr;
-    int rc = vhx_create(owner->device, &c);
-    if (rc) return rc;
-    c->tree = owner->tree;  // the same device tree (reference-counted); the context's fresh store goes with it
-    register_user(c);
-    c->shared = true;
-    copy_sched(c, owner);  // the owner's scheduling settings (as of now; vhx_mgpu re-copies them per frame)
-    *out = c;
-    return VHX_OK;
-}
-
-void vhx_destroy(vhx_ctx *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    unregister_user(c);
-    c->tree.reset();  // frees the device tree with its last context
-    if (c->use_ev) (void)hipEventDestroy(c->use_ev);
-    for (DevBuf *b : {&c->scratch, &c->rays, &c->queue[0], &c->queue[1], &c->qctl, &c->tmp, &c->counts, &c->offsets,
-                      &c->flags, &c->qargs, &c->state, &c->stateq, &c->upd, &c->prepass_depth, &c->batch_args, &c->scan_part,
-                      &c->shadow_args, &c->tail_list[0], &c->tail_list[1], &c->tail_mask, &c->build.occ, &c->build.rank,
-                      &c->build.first, &c->build.part, &c->build.table, &c->build.ctl, &c->build.grid,
-                      &c->build.simp})
-        if (b->ptr) (void)hipFree(b->ptr);
-    if (c->tail_stream) {
-        (void)hipStreamSynchronize(c->tail_stream);
-        (void)hipStreamDestroy(c->tail_stream);
-    }
-    if (c->tail_fork) (void)hipEventDestroy(c->tail_fork);
-    if (c->tail_join) (void)hipEventDestroy(c->tail_join);
-    std::vector<vhx_ctx::Pinned *> pins = {&c->pinned[0], &c->pinned[1]};
-    for (auto &P : c->batch_pinned) pins.push_back(&P);
-    for (auto &P : c->shadow_pinned) pins.push_back(&P);
-    for (auto *P : pins) {
-        if (P->ptr) (void)hipHostFree(P->ptr);
-        if (P->done) (void)hipEventDestroy(P->done);
-    }
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
-}
 
 int vhx_set_pass_budgets(vhx_ctx *c, const uint32_t *budgets, uint32_t n) {
     if (!c || n > VHX_MAX_BUDGETS || (n && !budgets)) return VHX_E_INVALID_ARG;
@@ -2078,571 +1905,6 @@ int vhx_set_pass_budgets(vhx_ctx *c, const uint32_t *budgets, uint32_t n) {
         c->adaptive = false;
     }
     c->last_sched = -1;
-    return VHX_OK;
-}
-
-// vhx_set_tuning: the scheduling knobs of the probes (they used to be environment variables read at vhx_create; the
-// library now reads none). Parsed into a copy of the context first, so a malformed spec changes nothing.
-static bool parse_u32_list(const std::string &v, uint32_t *out, uint32_t cap, uint32_t &n) {
-    n = 0;
-    const char *q = v.c_str();
-    if (!*q) return true;
-    for (;;) {
-        char *end = nullptr;
-        const unsigned long x = strtoul(q, &end, 10);
-        if (end == q || n >= cap || x > 0xFFFFFFFFul) return false;
-        out[n++] = (uint32_t)x;
-        if (*end == '\0') return true;
-        if (*end != ',') return false;
-        q = end + 1;
-    }
-}
-static bool parse_u32(const std::string &v, uint32_t &out) {
-    uint32_t n = 0, x[1];
-    if (!parse_u32_list(v, x, 1, n) || n != 1) return false;
-    out = x[0];
-    return true;
-}
-static int apply_tuning(vhx_ctx *c, const std::string &key, const std::string &val) {
-    uint32_t x = 0, n = 0, l[VHX_MAX_BUDGETS + 1];
-    auto bad = [&]() { return fail(c, VHX_E_INVALID_ARG, ("vhx_set_tuning: bad value for " + key).c_str()); };
-    if (key == "budgets") {  // "" or "0" = one pass
-        if (!parse_u32_list(val, l, VHX_MAX_BUDGETS, n)) return bad();
-        if (n == 1 && l[0] == 0) n = 0;
-        return vhx_set_pass_budgets(c, l, n);
-    } else if (key == "adaptive") {
-        if (!parse_u32(val, x) || x > 1) return bad();
-        return vhx_set_adaptive_schedule(c, (int)x);
-    } else if (key == "rpw") {  // queue passes 1.., 0 = adaptive
-        if (!parse_u32_list(val, l, VHX_MAX_BUDGETS, n)) return bad();
-        for (uint32_t i = 0; i < n; ++i) {
-            if (l[i] > 64) return bad();
-            c->rpw[i + 1] = l[i];
-        }
-    } else if (key == "tw") {
-        if (!parse_u32(val, x) || x == 0) return bad();
-        c->tw = x;
-    } else if (key == "xcdg") {
-        if (!parse_u32(val, x)) return bad();
-        c->xcd_group = x;
-    } else if (key == "resume") {
-        if (!parse_u32(val, x) || x > 1) return bad();
-        c->resume = x != 0;
-    } else if (key == "tlists") {
-        if (!parse_u32(val, x) || x > 1) return bad();
-        c->tile_lists = x != 0;
-    } else if (key == "qstate") {
-        if (!parse_u32(val, x) || x > 1) return bad();
-        c->qstate = x != 0;
-    } else if (key == "save_from") {
-        if (!parse_u32(val, x)) return bad();
-        c->save_from = x;
-    } else if (key == "qblock") {
-        if (!parse_u32(val, x) || (x != 64 && x != 128 && x != 256)) return bad();
-        c->qblock = x;
-    } else if (key == "qwaves") {  // fixes the schedule
-        if (!parse_u32(val, x) || x == 0) return bad();
-        if (c->adaptive) vhx_set_adaptive_schedule(c, 0);
-        c->queue_waves = x;
-    } else if (key == "qwpc_idle" || key == "qwpc_busy") {  // queue waves per CU of one schedule (stays adaptive)
-        if (!parse_u32(val, x) || x == 0 || x > 64) return bad();
-        (key == "qwpc_idle" ? c->sched_idle : c->sched_busy).queue_waves_per_cu = x;
-    } else if (key == "qwavesm") {
-        if (!parse_u32(val, x)) return bad();
-        c->queue_waves_mid = x;
-    } else if (key == "p0lists") {  // pass 0 of primary frames: 1 = lists in the queue order (ListOrder), 0 = flags
-        if (!parse_u32(val, x) || x > 1) return bad();
-        c->p0lists = x != 0;
-    } else if (key == "scan_multi") {  // 0 = every scan on one workgroup
-        if (!parse_u32(val, x)) return bad();
-        c->scan_multi = x;
-    } else if (key == "tail") {  // early tail of lone frames (vhx_ctx::tail_*): 1 on, 0 off
-        if (!parse_u32(val, x) || x > 1) return bad();
-        c->tail_on = x != 0;
-    } else if (key == "tail_min") {  // steps from which a ray joins the next lone frame's early tail
-        if (!parse_u32(val, x) || x == 0) return bad();
-        c->tail_min = x;
-    } else if (key == "tail_rpw") {  // early-tail rays per wave
-        if (!parse_u32(val, x) || x == 0 || x > 64) return bad();
-        c->tail_rpw = x;
-    } else if (key == "tail_prio") {  // s_setprio of the early-tail waves (0-3)
-        if (!parse_u32(val, x) || x > 3) return bad();
-        c->tail_prio = x;
-    } else if (key == "tail_cap") {  // longest list recorded
-        if (!parse_u32(val, x) || x > (1u << 20)) return bad();
-        c->tail_cap = x;
-        c->tail_valid = false;  // (a list recorded under another cap may hold more entries)
-    } else if (key == "finter") {  // batches: pass-0 blocks of the frames interleaved (1) or frame-major (0)
-        if (!parse_u32(val, x) || x > 1) return bad();
-        c->frame_interleave = x != 0;
-    } else if (key == "stage_slots") {  // batch staging ring slots in use (1 = wait for the previous batch's copy)
-        if (!parse_u32(val, x) || x == 0 || x > vhx_ctx::VHX_STAGE_SLOTS) return bad();
-        c->stage_slots = x;
-    } else if (key == "sbudget") {  // fused shadows: steps of a shadow ray in its primary ray's pass (0 = the rest)
-        if (!parse_u32(val, x)) return bad();
-        c->shadow_budget = x;
-    } else if (key == "qwaves0") {
-        if (!parse_u32(val, x) || x == 0) return bad();
-        c->queue_waves0 = c->queue_waves0_force = x;
-    } else if (key == "qxcd") {
-        if (!parse_u32(val, x)) return bad();
-        c->qxcd = x;
-    } else if (key == "qxcd_all") {
-        if (!parse_u32(val, x) || x > 1) return bad();
-        c->qxcd_all = x != 0;
-    } else if (key == "sparse") {  // per budgeted pass; fixes the schedule
-        if (!parse_u32_list(val, l, VHX_MAX_BUDGETS, n)) return bad();
-        for (uint32_t i = 0; i < n; ++i)
-            if (l[i] > 64) return bad();
-        if (c->adaptive) vhx_set_adaptive_schedule(c, 0);
-        for (uint32_t i = 0; i < VHX_MAX_BUDGETS; ++i) c->sparse[i] = i < n ? l[i] : 0u;
-    } else if (key == "qorder") {  // "[m]N[z|r]": NxN tiles, (m) Morton order of the tiles, (z) Morton / (r) rows inside
-        const bool m = !val.empty() && val[0] == 'm';
-        char *end = nullptr;
-        const char *b = val.c_str() + (m ? 1 : 0);
-        const long ts = strtol(b, &end, 10);
-        if (end == b) return bad();
-        const bool z = *end == 'z', rows = *end == 'r';
-        if (*end && !((z || rows) && end[1] == '\0')) return bad();
-        uint32_t lg = 0;
-        while (lg < 12u && (1l << lg) < ts) ++lg;
-        uint32_t code = 0;
-        if (ts != 0) {
-            if (ts < 8 || ts > 4096 || (1l << lg) != ts) return bad();
-            code = lg | (m ? 16u : 0u) | (z ? 32u : 0u) | (rows ? 64u : 0u);
-        }
-        c->qorder = c->sched_busy.qorder = c->sched_idle.qorder = code;  // both schedules (the rest stays adaptive)
-    } else if (key == "qsort") {  // segment length of the queue passes' node sort: 0 = off, else 256 .. VHX_QSORT_MAX
-        if (!parse_u32(val, x) || (x && (x < 256 || x > VHX_QSORT_MAX || (x & (x - 1))))) return bad();
-        c->qsort_force = (int)x;
-    } else if (key == "qsortp") {  // bit mask of the queue passes whose input is sorted
-        if (!parse_u32(val, x)) return bad();
-        c->qsort_passes = x;
-    } else if (key == "qsortb") {
-        if (!parse_u32(val, x) || x == 0) return bad();
-        c->qsort_blocks = x;
-    } else {
-        return fail(c, VHX_E_INVALID_ARG, ("vhx_set_tuning: unknown key " + key).c_str());
-    }
-    return VHX_OK;
-}
-
-int vhx_set_tuning(vhx_ctx *c, const char *spec) {
-    if (!c || !spec) return VHX_E_INVALID_ARG;
-    std::vector<std::pair<std::string, std::string>> kv;
-    for (const char *q = spec; *q;) {
-        const char *e = q;
-        while (*e && *e != ';') ++e;
-        const std::string item(q, e);
-        q = *e ? e + 1 : e;
-        if (item.empty()) continue;
-        const size_t eq = item.find('=');
-        if (eq == std::string::npos || eq == 0) return fail(c, VHX_E_INVALID_ARG, "vhx_set_tuning: expected key=value");
-        kv.emplace_back(item.substr(0, eq), item.substr(eq + 1));
-    }
-    // a dry run on a scratch context first: a malformed spec leaves c unchanged
-    {
-        vhx_ctx dry;
-        copy_sched(&dry, c);
-        for (const auto &p : kv) {
-            const int rc = apply_tuning(&dry, p.first, p.second);
-            if (rc) {
-                c->err = dry.err;
-                return rc;
-            }
-        }
-    }
-    for (const auto &p : kv) {
-        const int rc = apply_tuning(c, p.first, p.second);
-        if (rc) return rc;
-    }
-    return VHX_OK;
-}
-
-int vhx_set_adaptive_schedule(vhx_ctx *c, int on) {
-    if (!c) return VHX_E_INVALID_ARG;
-    if (!on && c->adaptive) {  // leaving the adaptive choice: the frames-in-flight schedule, whatever the last trace ran
-        const vhx_ctx::Sched &s = c->sched_busy;
-        std::memcpy(c->budgets, s.budgets, sizeof(c->budgets));
-        std::memcpy(c->sparse, s.sparse, sizeof(c->sparse));
-        c->npass = s.npass;
-        c->queue_waves = s.queue_waves_per_cu * c->cus;
-        c->queue_waves0 = c->queue_waves0_force ? c->queue_waves0_force : s.queue_waves0_per_cu * c->cus;
-        c->qorder = s.qorder;
-        c->last_sched = -1;
-    }
-    c->adaptive = on != 0;
-    return VHX_OK;
-}
-
-int vhx_get_pass_budgets(const vhx_ctx *c, uint32_t *budgets, uint32_t *n, int *sched) {
-    if (!c || !n) return VHX_E_INVALID_ARG;
-    *n = c->npass > 0 ? c->npass - 1 : 0;
-    if (budgets)
-        for (uint32_t i = 0; i < VHX_MAX_BUDGETS; ++i) budgets[i] = i < *n ? c->budgets[i] : 0u;
-    if (sched) *sched = c->last_sched;
-    return VHX_OK;
-}
-
-const char *vhx_last_error(const vhx_ctx *c) { return c ? c->err.c_str() : "null context"; }
-
-int vhx_set_stream(vhx_ctx *c, void *s) {
-    if (!c) return VHX_E_INVALID_ARG;
-    c->stream = s ? (hipStream_t)s : c->own_stream;  // null own stream: created at the next use
-    c->qargs_host_ptr[0] = c->qargs_host_ptr[1] = nullptr;  // written on the previous stream: rewrite them
-    return VHX_OK;
-}
-
-int vhx_get_stream(vhx_ctx *c, void **s) {
-    if (!c || !s) return VHX_E_INVALID_ARG;
-    VHX_HIP(c, hipSetDevice(c->device));
-    VHX_STREAM(c);
-    *s = (void *)c->stream;
-    return VHX_OK;
-}
-
-int vhx_sync(vhx_ctx *c, float *ms) {
-    if (!c) return VHX_E_INVALID_ARG;
-    VHX_HIP(c, hipSetDevice(c->device));
-    if (c->stream) VHX_HIP(c, hipStreamSynchronize(c->stream));
-    if (ms) {
-        *ms = 0.f;
-        if (c->timed) VHX_HIP(c, hipEventElapsedTime(ms, c->ev0, c->ev1));
-    }
-    return VHX_OK;
-}
-
-}  // extern "C"
-
-int vhx::launch_untile(vhx_ctx *c, hipStream_t stream, const void *gathered, uint32_t planes, uint32_t ranks,
-                       uint32_t tiles_per_rank, uint32_t T, uint32_t width, uint32_t height, uint32_t *fb_rgba,
-                       float *fb_depth) {
-    const uint32_t tiles_x = (width + T - 1) / T, tiles_y = (height + T - 1) / T;
-    const uint64_t n = (uint64_t)ranks * planes * tiles_per_rank * T * T;
-    if (n == 0) return VHX_OK;
-    k_untile_planes<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>((const uint32_t *)gathered, planes, ranks,
-                                                                     tiles_per_rank, T, tiles_x, tiles_x * tiles_y,
-                                                                     width, height, fb_rgba, (uint32_t *)fb_depth);
-    VHX_HIP(c, hipGetLastError());
-    return VHX_OK;
-}
-
-int vhx::alloc_tree(vhx_ctx *c, const vhx_tree_desc *t) {
-    const uint32_t bd = t->brick_dim;
-    if (t->node_count == 0 || bd == 0 || t->boxtree_size == 0 || (bd & (bd - 1)) != 0 || bd > 32 ||
-        (t->boxtree_size & (t->boxtree_size - 1)) != 0 || t->boxtree_size > (1u << 24))
-        return fail(c, VHX_E_INVALID_ARG, "vhx_upload_tree: invalid sizes");
-    VHX_HIP(c, hipSetDevice(c->device));
-    // a buffer that grows is freed and reallocated: the frames in flight on the tree's contexts (which c's stream
-    // already waits for, write_begin) finish first
-    bool grows = false;
-    for (int id = 0; id < 7; ++id) grows |= c->tree->raw[id].bytes < elem_count(*t, id) * elem_size(id);
-    if (grows && c->stream) VHX_HIP(c, hipStreamSynchronize(c->stream));
-    c->tree->uploaded = false;
-    c->tree->mips_on = false;  // a new tree has no MIPs until vhx_set_node_mips
-    for (int id = 0; id < 7; ++id) {
-        int rc = ensure(c, c->tree->raw[id], elem_count(*t, id) * elem_size(id));
-        if (rc) return rc;
-    }
-    c->tree->desc = *t;
-    for (const void **q : {(const void **)&c->tree->desc.node_type, (const void **)&c->tree->desc.node_ocbits,
-                           (const void **)&c->tree->desc.node_children, (const void **)&c->tree->desc.voxels,
-                           (const void **)&c->tree->desc.solid_values, (const void **)&c->tree->desc.color_palette,
-                           (const void **)&c->tree->desc.data_palette})
-        *q = nullptr;  // only the counts are kept
-    return VHX_OK;
-}
-
-int vhx::finish_upload(vhx_ctx *c) {
-    const vhx_tree_desc *t = &c->tree->desc;
-    const uint64_t bd = t->brick_dim, n3 = bd * bd * bd;
-    c->tree->occ_words = n3 >= 64 ? (uint32_t)(n3 / 64) : 1u;
-    int rc = ensure(c, c->tree->hdr, (uint64_t)t->node_count * 16);
-    if (rc) return rc;
-    rc = ensure(c, c->tree->brick_occ, (uint64_t)t->brick_count * c->tree->occ_words * 8);
-    if (rc) return rc;
-    if ((rc = rebuild_hdr(c, 0, t->node_count))) return rc;
-    if ((rc = rebuild_occ(c, 0, t->brick_count))) return rc;
-    if (has_child_rec(c)) {
-        if ((rc = ensure(c, c->tree->child_rec, (uint64_t)t->node_count * 64 * 16))) return rc;
-        c->tree->child_rec_stale = true;
-        if ((rc = refresh_child_rec(c))) return rc;
-    }
-    VHX_HIP(c, hipStreamSynchronize(c->stream));
-    c->tree->uploaded = true;
-    return VHX_OK;
-}
-
-extern "C" {
-
-int vhx_upload_tree(vhx_ctx *c, const vhx_tree_desc *t) {
-    if (!c || !t) return VHX_E_INVALID_ARG;
-    if (c->shared) return fail(c, VHX_E_STATE, "vhx_upload_tree on a shared context: upload through the owner");
-    const void *src[7] = {t->node_type, t->node_ocbits, t->node_children, t->voxels,
-                          t->solid_values, t->color_palette, t->data_palette};
-    for (int id = 0; id < 7; ++id)
-        if (elem_count(*t, id) && !src[id])
-            return fail(c, VHX_E_INVALID_ARG, "vhx_upload_tree: null array with non-zero count");
-    VHX_HIP(c, hipSetDevice(c->device));
-    VHX_STREAM(c);
-    WriteScope ws(c);  // frames in flight on the tree's other contexts finish reading it first
-    int rc = ws.rc;
-    if (!rc) rc = alloc_tree(c, t);
-    if (rc) return rc;
-    for (int id = 0; id < 7; ++id) {
-        const uint64_t bytes = elem_count(*t, id) * elem_size(id);
-        if (bytes) VHX_HIP(c, hipMemcpyAsync(c->tree->raw[id].ptr, src[id], bytes, hipMemcpyHostToDevice, c->stream));
-    }
-    if ((rc = finish_upload(c))) return rc;
-    return ws.end();
-}
-
-}  // extern "C"
-
-int vhx::receive_tree(vhx_ctx *c, const vhx_tree_desc &counts,
-                      int (*fill)(void *, void *const[7], const uint64_t[7]), void *arg) {
-    VHX_HIP(c, hipSetDevice(c->device));
-    VHX_STREAM(c);
-    WriteScope ws(c);
-    int rc = ws.rc;
-    if (!rc) rc = alloc_tree(c, &counts);
-    if (rc) return rc;
-    void *dst[7];
-    uint64_t bytes[7];
-    for (int id = 0; id < 7; ++id) {
-        dst[id] = c->tree->raw[id].ptr;
-        bytes[id] = elem_count(c->tree->desc, id) * elem_size(id);
-    }
-    if ((rc = fill(arg, dst, bytes))) return rc;  // the transfers, enqueued on c's stream
-    if ((rc = finish_upload(c))) return rc;       // derived layout from the received buffers (synchronises)
-    return ws.end();
-}
-
-void vhx::copy_sched(vhx_ctx *c, const vhx_ctx *owner) {
-    std::memcpy(c->budgets, owner->budgets, sizeof(c->budgets));
-    std::memcpy(c->rpw, owner->rpw, sizeof(c->rpw));
-    c->npass = owner->npass;
-    c->tw = owner->tw;
-    c->scan_multi = owner->scan_multi;
-    c->p0lists = owner->p0lists;
-    c->resume = owner->resume;
-    c->qstate = owner->qstate;
-    c->tile_lists = owner->tile_lists;
-    c->save_from = owner->save_from;
-    c->qorder = owner->qorder;
-    c->adaptive = owner->adaptive;
-    c->sched_busy = owner->sched_busy;
-    c->sched_idle = owner->sched_idle;
-    c->cus = owner->cus;
-    c->xcd_group = owner->xcd_group;
-    c->qblock = owner->qblock;
-    c->queue_blocks = owner->queue_blocks;
-    c->queue_waves = owner->queue_waves;
-    c->queue_waves0 = owner->queue_waves0;
-    c->queue_waves0_force = owner->queue_waves0_force;
-    c->shadow_budget = owner->shadow_budget;
-    c->stage_slots = owner->stage_slots;
-    c->frame_interleave = owner->frame_interleave;
-    c->tail_on = owner->tail_on;
-    c->tail_min = owner->tail_min;
-    c->tail_rpw = owner->tail_rpw;
-    c->tail_prio = owner->tail_prio;
-    if (c->tail_cap != owner->tail_cap) c->tail_valid = false;
-    c->tail_cap = owner->tail_cap;
-    c->queue_waves_mid = owner->queue_waves_mid;
-    c->qxcd = owner->qxcd;
-    c->qxcd_all = owner->qxcd_all;
-    c->qsort_force = owner->qsort_force;
-    c->qsort_passes = owner->qsort_passes;
-    c->qsort_blocks = owner->qsort_blocks;
-    std::memcpy(c->sparse, owner->sparse, sizeof(c->sparse));
-    c->prepass = owner->prepass;
-    c->prepass_margin = owner->prepass_margin;
-    c->shadow_on = owner->shadow_on;
-    std::memcpy(c->shadow_light, owner->shadow_light, sizeof(c->shadow_light));
-}
-
-extern "C" {
-
-static int fill_device_copies(void *arg, void *const dst[7], const uint64_t bytes[7]) {
-    const std::pair<vhx_ctx *, const vhx_tree_desc *> &a = *(const std::pair<vhx_ctx *, const vhx_tree_desc *> *)arg;
-    vhx_ctx *c = a.first;
-    const void *src[7] = {a.second->node_type,  a.second->node_ocbits,    a.second->node_children, a.second->voxels,
-                          a.second->solid_values, a.second->color_palette, a.second->data_palette};
-    for (int id = 0; id < 7; ++id)
-        if (bytes[id]) VHX_HIP(c, hipMemcpyAsync(dst[id], src[id], bytes[id], hipMemcpyDefault, c->stream));
-    return VHX_OK;
-}
-
-int vhx_upload_tree_device(vhx_ctx *c, const vhx_tree_desc *t) {
-    if (!c || !t) return VHX_E_INVALID_ARG;
-    if (c->shared) return fail(c, VHX_E_STATE, "vhx_upload_tree_device on a shared context: upload through the owner");
-    const void *src[7] = {t->node_type, t->node_ocbits, t->node_children, t->voxels,
-                          t->solid_values, t->color_palette, t->data_palette};
-    for (int id = 0; id < 7; ++id)
-        if (elem_count(*t, id) && !src[id])
-            return fail(c, VHX_E_INVALID_ARG, "vhx_upload_tree_device: null array with non-zero count");
-    std::pair<vhx_ctx *, const vhx_tree_desc *> arg{c, t};
-    return receive_tree(c, *t, fill_device_copies, &arg);
-}
-
-int vhx_update_ranges(vhx_ctx *c, const vhx_range *r, uint32_t n) {
-    if (!c || (n && !r)) return VHX_E_INVALID_ARG;
-    if (c->shared) return fail(c, VHX_E_STATE, "vhx_update_range(s) on a shared context: update through the owner");
-    if (!c->tree->uploaded) return fail(c, VHX_E_STATE, "vhx_update_range(s) before vhx_upload_tree");
-    // validate every range first: a failing call writes nothing
-    uint64_t data_bytes = 0, njobs = 0;
-    for (uint32_t k = 0; k < n; ++k) {
-        if (r[k].buffer_id < 0 || r[k].buffer_id > 6 || (!r[k].src && r[k].elem_count)) return VHX_E_INVALID_ARG;
-        const uint64_t cap = elem_count(c->tree->desc, r[k].buffer_id);
-        if (r[k].elem_offset > cap || r[k].elem_count > cap - r[k].elem_offset)
-            return fail(c, VHX_E_CAPACITY, "vhx_update_range(s): range beyond the uploaded buffer");
-        const uint64_t bytes = r[k].elem_count * elem_size(r[k].buffer_id);
-        data_bytes += (bytes + 15) & ~15ull;
-        njobs += (bytes + UPD_PIECE_BYTES - 1) / UPD_PIECE_BYTES;
-    }
-    if (data_bytes == 0) return VHX_OK;
-    if (njobs > 0xFFFFFFFFull) return fail(c, VHX_E_INVALID_ARG, "vhx_update_ranges: too much data in one call");
-    VHX_HIP(c, hipSetDevice(c->device));
-    VHX_STREAM(c);
-    // the scatter and the derived-state rebuilds write the tree: frames in flight on the other contexts first
-    WriteScope ws(c);
-    int rc = ws.rc;
-    if (rc) return rc;
-    // pinned staging slot (the one used two calls ago: its copy has normally long completed)
-    vhx_ctx::Pinned &P = c->pinned[c->pinned_next];
-    c->pinned_next ^= 1u;
-    if (P.used) VHX_HIP(c, hipEventSynchronize(P.done));
-    const uint64_t jobs_bytes = (njobs * sizeof(UpdJob) + 255) & ~255ull, total = jobs_bytes + data_bytes;
-    if (P.bytes < total) {
-        if (P.ptr) VHX_HIP(c, hipHostFree(P.ptr));
-        P.ptr = nullptr;
-        P.bytes = 0;
-        const uint64_t want = std::max<uint64_t>(total + total / 4, 1ull << 20);
-        VHX_HIP(c, hipHostMalloc(&P.ptr, want, hipHostMallocDefault));
-        P.bytes = want;
-    }
-    if (!P.done) VHX_HIP(c, hipEventCreateWithFlags(&P.done, hipEventDisableTiming));
-    // the device staging buffer: the previous batch's scatter may still read it (on this stream, or on the stream the
-    // context used then), so a growth or a stream change waits for it
-    if (c->upd_stream && (c->upd_stream != c->stream || c->upd.bytes < P.bytes))
-        VHX_HIP(c, hipStreamSynchronize(c->upd_stream));
-    rc = ensure(c, c->upd, P.bytes);
-    if (rc) return rc;
-    c->upd_stream = c->stream;
-    // pack: the job table, then each range's data (16-byte aligned)
-    UpdJob *jobs = (UpdJob *)P.ptr;
-    uint64_t off = jobs_bytes, j = 0;
-    // ranges of one scatter launch are written in no particular order, so a range that overlaps an earlier range of
-    // the call starts a new launch (launches on a stream run in order: the later write wins, as in a sequence of
-    // write_range_to_buffer calls)
-    std::vector<uint32_t> group_start{0};
-    std::vector<std::pair<uint64_t, uint64_t>> group_spans[7];  // byte spans of the current group, per buffer
-    uint32_t node_lo = UINT32_MAX, node_hi = 0, hdr_lo = UINT32_MAX, hdr_hi = 0, brick_lo = UINT32_MAX, brick_hi = 0;
-    bool palette = false;
-    const uint64_t n3 = (uint64_t)c->tree->desc.brick_dim * c->tree->desc.brick_dim * c->tree->desc.brick_dim;
-    for (uint32_t k = 0; k < n; ++k) {
-        const int id = r[k].buffer_id;
-        const uint64_t es = elem_size(id), bytes = r[k].elem_count * es;
-        if (!bytes) continue;
-        std::memcpy((uint8_t *)P.ptr + off, r[k].src, bytes);
-        const uint64_t dst = (uint64_t)(uintptr_t)c->tree->raw[id].ptr + r[k].elem_offset * es;
-        {
-            const uint64_t b0 = r[k].elem_offset * es, b1 = b0 + bytes;
-            bool overlaps = false;
-            for (const auto &sp : group_spans[id]) overlaps |= b0 < sp.second && sp.first < b1;
-            if (overlaps) {
-                group_start.push_back((uint32_t)j);
-                for (auto &g : group_spans) g.clear();
-            }
-            group_spans[id].push_back({b0, b1});
-        }
-        for (uint64_t p = 0; p < bytes; p += UPD_PIECE_BYTES) {
-            UpdJob &jb = jobs[j++];
-            jb.dst = dst + p;
-            jb.src_off = off + p;
-            jb.words = (uint32_t)(std::min<uint64_t>(UPD_PIECE_BYTES, bytes - p) / 4);
-            jb.pad0 = 0;
-            jb.pad1 = 0;
-        }
-        off += (bytes + 15) & ~15ull;
-        const uint64_t e0 = r[k].elem_offset, e1 = e0 + r[k].elem_count;
-        if (id == VHX_BUF_NODE_TYPE || id == VHX_BUF_NODE_OCBITS) {
-            hdr_lo = std::min<uint32_t>(hdr_lo, (uint32_t)e0);
-            hdr_hi = std::max<uint32_t>(hdr_hi, (uint32_t)e1);
-        }
-        if (id == VHX_BUF_NODE_TYPE) {
-            node_lo = std::min<uint32_t>(node_lo, (uint32_t)e0);
-            node_hi = std::max<uint32_t>(node_hi, (uint32_t)e1);
-        } else if (id == VHX_BUF_NODE_CHILDREN) {
-            node_lo = std::min<uint32_t>(node_lo, (uint32_t)(e0 / 64));
-            node_hi = std::max<uint32_t>(node_hi, (uint32_t)((e1 + 63) / 64));
-        } else if (id == VHX_BUF_VOXELS) {
-            brick_lo = std::min<uint32_t>(brick_lo, (uint32_t)(e0 / n3));
-            brick_hi = std::max<uint32_t>(brick_hi, (uint32_t)((e1 + n3 - 1) / n3));
-        } else if (id == VHX_BUF_COLOR_PALETTE || id == VHX_BUF_DATA_PALETTE) {
-            palette = true;
-        }
-    }
-    // one host-to-device copy of the packed batch, one scatter kernel
-    VHX_HIP(c, hipMemcpyAsync(c->upd.ptr, P.ptr, total, hipMemcpyHostToDevice, c->stream));
-    VHX_HIP(c, hipEventRecord(P.done, c->stream));
-    P.used = true;
-    group_start.push_back((uint32_t)j);
-    for (size_t g = 0; g + 1 < group_start.size(); ++g) {
-        const uint32_t j0 = group_start[g], j1 = group_start[g + 1];
-        if (j1 > j0)
-            k_scatter_ranges<<<std::min<uint32_t>(j1 - j0, 8192u), 256, 0, c->stream>>>((const uint8_t *)c->upd.ptr,
-                                                                                         j0, j1);
-    }
-    VHX_HIP(c, hipGetLastError());
-    // derived state, stream-ordered
-    if (hdr_lo < hdr_hi && (rc = rebuild_hdr(c, hdr_lo, hdr_hi - hdr_lo))) return rc;
-    if (palette) {
-        // emptiness of any cell may change: every bitmap and record
-        if ((rc = rebuild_occ(c, 0, c->tree->desc.brick_count))) return rc;
-        c->tree->child_rec_stale = true;
-        rc = refresh_child_rec(c);
-    } else {
-        if (brick_lo < brick_hi && (rc = rebuild_occ(c, brick_lo, brick_hi - brick_lo))) return rc;
-        rc = refresh_child_rec_sel(c, node_lo, node_hi, brick_lo, brick_hi);
-    }
-    if (rc) return rc;
-    return ws.end();  // the next trace of every context of the tree waits for this write
-}
-
-int vhx_update_range(vhx_ctx *c, int id, uint64_t off, uint64_t count, const void *src) {
-    if (!c || id < 0 || id > 6 || (!src && count)) return VHX_E_INVALID_ARG;
-    vhx_range r{};
-    r.buffer_id = id;
-    r.elem_offset = off;
-    r.elem_count = count;
-    r.src = src;
-    return vhx_update_ranges(c, &r, 1);
-}
-
-int vhx_read_derived(vhx_ctx *c, int which, uint64_t off, uint64_t count, void *dst) {
-    if (!c || (!dst && count) || which < 0 || which > 1) return VHX_E_INVALID_ARG;
-    if (!c->tree->uploaded) return fail(c, VHX_E_STATE, "vhx_read_derived before vhx_upload_tree");
-    const uint64_t es = which == VHX_DERIVED_NODE_HDR ? 16 : 8;
-    const uint64_t cap = which == VHX_DERIVED_NODE_HDR ? c->tree->desc.node_count
-                                                       : (uint64_t)c->tree->desc.brick_count * c->tree->occ_words;
-    if (off + count > cap) return fail(c, VHX_E_CAPACITY, "vhx_read_derived: range beyond the buffer");
-    const DevBuf &b = which == VHX_DERIVED_NODE_HDR ? c->tree->hdr : c->tree->brick_occ;
-    VHX_HIP(c, hipSetDevice(c->device));
-    VHX_STREAM(c);
-    TraceScope tscope(c);  // after the tree's last write
-    if (tscope.rc) return tscope.rc;
-    VHX_HIP(c, hipMemcpyAsync(dst, (const char *)b.ptr + off * es, count * es, hipMemcpyDeviceToHost, c->stream));
-    VHX_HIP(c, hipStreamSynchronize(c->stream));
-    return tscope.end();
-}
-
-int vhx_tree_device_bytes(const vhx_ctx *c, uint64_t *bytes) {
-    if (!c || !bytes) return VHX_E_INVALID_ARG;
-    uint64_t b = c->tree->hdr.bytes + c->tree->brick_occ.bytes + c->tree->child_rec.bytes;
-    for (auto &r : c->tree->raw) b += r.bytes;
-    *bytes = b;
     return VHX_OK;
 }
 
@@ -2689,20 +1951,17 @@ int vhx_trace_primary(vhx_ctx *c, const vhx_camera *cam, uint32_t T, uint32_t ti
     const uint32_t bpx = (T + 15) / 16, bpt = bpx * bpx;
     const uint64_t nblocks = (uint64_t)my_tiles * bpt;
     if (nblocks > 0x7FFFFFFFull) return fail(c, VHX_E_INVALID_ARG, "frame too large");
-    const uint64_t nout = layout == VHX_LAYOUT_FRAMEBUFFER ? (uint64_t)cam->width * cam->height
-                                                           : (uint64_t)my_tiles * T * T;
-    VHX_HIP(c, hipSetDevice(c->device));
-    VHX_STREAM(c);
-    // after the tree's last write (an update through the owner, on its stream); the prepass's inner frame runs inside
-    // the outer frame's scope
-    TraceScope tscope(c, c->in_prepass);
-    int rc = tscope.rc;
+    const bool fb = layout == VHX_LAYOUT_FRAMEBUFFER;
+    const bool whole_fb = fb && tile_start == 0 && tile_stride == 1;  // the whole frame in the framebuffer layout ...
+    const bool whole_fb16 = whole_fb && T == 16;                      // ... a 16x16 block per tile
+    const uint64_t nout = fb ? (uint64_t)cam->width * cam->height : (uint64_t)my_tiles * T * T;
+    TraceCall tr(c, c->in_prepass);
+    int rc = tr.rc;
     if (rc) return rc;
     HostOut ho;
-    rc = map_out(c, out, nout, on_device, ho, layout == VHX_LAYOUT_TILES);
-    if (rc) return rc;
-    if ((rc = refresh_child_rec(c))) return rc;
-    const DevTree t = dev_tree(c);
+    if ((rc = map_out(c, out, nout, on_device, ho, layout == VHX_LAYOUT_TILES))) return rc;
+    DevTree t;
+    if ((rc = tr.tree(t))) return rc;
     if (t.mips && (out->bytes || (c->prepass && !c->in_prepass)))
         return fail(c, VHX_E_INVALID_ARG, "vhx_trace_primary: byte counting and the depth prepass are not available "
                                           "with node MIPs (vhx_set_node_mips)");
@@ -2711,14 +1970,12 @@ int vhx_trace_primary(vhx_ctx *c, const vhx_camera *cam, uint32_t T, uint32_t ti
     if (shadows && (!out->value || !out->impact || !out->normal || !out->shadowed || out->bytes || t.mips || c->prepass))
         return fail(c, VHX_E_INVALID_ARG, "vhx_trace_primary with a shadow light: value, impact, normal and shadowed "
                                           "outputs needed; no byte counting, node MIPs or depth prepass");
-    const CamD cd = cam_of(cam);
     uint32_t npass = 1;
-    rc = prepare_passes(c, nout, nblocks, npass);
-    if (rc) return rc;
+    if ((rc = prepare_passes(c, nout, nblocks, npass))) return rc;
     // pass 0's list buffers for either schedule's queue order: a context's first frames often run alone (the idle
     // schedule), and growing the buffers at its first frame among others would hipFree -- a device-wide
     // synchronisation that drains every frame in flight (measured: 0.61 against 0.54 ms per bench frame)
-    if (c->p0lists && layout == VHX_LAYOUT_FRAMEBUFFER && T == 16 && tile_start == 0 && tile_stride == 1) {
+    if (c->p0lists && whole_fb16) {
         const uint32_t orders[2] = {c->sched_busy.qorder, c->qorder};
         for (uint32_t o : orders) {
             ListOrder l2{};
@@ -2726,165 +1983,71 @@ int vhx_trace_primary(vhx_ctx *c, const vhx_camera *cam, uint32_t T, uint32_t ti
             if (list_order(o, cam->width, cam->height, l2, nb2) && (rc = ensure_lists(c, nb2))) return rc;
         }
     }
-    RaySrc src{};
-    src.kind = layout == VHX_LAYOUT_FRAMEBUFFER ? 0u : 1u;
-    src.T = T;
-    src.tiles_x = tiles_x;
-    src.tile_start = tile_start;
-    src.tile_stride = tile_stride;
-    if (!c->in_prepass) VHX_HIP(c, hipEventRecord(c->ev0, c->stream));
+    if ((rc = tr.start())) return rc;
     // depth-prepass mode (vhx_set_depth_prepass): a whole framebuffer frame without byte counting first traces the
-    // half-resolution depth frame (a nested call, same stream), then the full frame starts from it
-    const bool fast = c->prepass && !c->in_prepass && layout == VHX_LAYOUT_FRAMEBUFFER && tile_start == 0 &&
-                      tile_stride == 1 && !out->bytes;
+    // half-resolution depth frame, then starts from it
+    const bool fast = c->prepass && !c->in_prepass && whole_fb && !out->bytes;
     FastD fd{};
-    if (fast) {
-        vhx_camera hc = *cam;
-        hc.width = (cam->width + 1) / 2;
-        hc.height = (cam->height + 1) / 2;
-        if (cam->ray_model == VHX_RAY_GLASS) {
-            // texel (X, Y) looks through the centre of full pixels 2X..2X+1, 2Y..2Y+1 (y counted upward in the glass)
-            const float ox = 0.5f * cam->pixel_width, oy = ((float)cam->height + 0.5f - 2.0f * (float)hc.height) * cam->pixel_height;
-            for (int k = 0; k < 3; ++k)
-                hc.glass_bottom_left[k] = cam->glass_bottom_left[k] + cam->glass_right[k] * ox + cam->glass_up[k] * oy;
-            hc.pixel_width = 2.0f * cam->pixel_width;
-            hc.pixel_height = 2.0f * cam->pixel_height;
-        }
-        int rc2 = ensure(c, c->prepass_depth, (uint64_t)hc.width * hc.height * 4);
-        if (rc2) return rc2;
-        vhx_hits dh{};
-        dh.depth = (float *)c->prepass_depth.ptr;
-        c->in_prepass = true;
-        rc2 = vhx_trace_primary(c, &hc, 0, 0, 1, VHX_LAYOUT_FRAMEBUFFER, &dh, 1);
-        c->in_prepass = false;
-        if (rc2) return rc2;
-        fd = FastD{(const float *)c->prepass_depth.ptr, hc.width, hc.height, c->prepass_margin};
-    }
+    if (fast && (rc = trace_prepass(c, cam, fd))) return rc;
     // no reset_passes: the flag compaction after pass 0 zeroes the queue passes' counters.
     // A rank-sharded framebuffer (tile_start > 0 or tile_stride > 1) leaves the flags of other ranks' pixels unwritten,
     // while the compaction scans every pixel: they are cleared first (stale flags would queue foreign pixels)
-    if (npass > 1 && layout == VHX_LAYOUT_FRAMEBUFFER && (tile_start > 0 || tile_stride > 1))
-        VHX_HIP(c, hipMemsetAsync(c->flags.ptr, 0, nout, c->stream));
+    if (npass > 1 && fb && !whole_fb) VHX_HIP(c, hipMemsetAsync(c->flags.ptr, 0, nout, c->stream));
 
-    const bool count = ho.dev.bytes != nullptr;
-    int qrc = VHX_OK;
+    // a whole framebuffer frame in the default queue order lists its rays in that order itself; a tile set (the rank's
+    // share of a multi-GPU frame) lists them under the frames-in-flight schedule (a queue order is in force)
+    Pass0Plan p0;
+    if ((rc = plan_pass0(c, npass, whole_fb16, layout == VHX_LAYOUT_TILES && c->qorder != 0, cam->width, cam->height,
+                         nblocks, 1, shadows, true, p0)))
+        return rc;
+    QueueRun run;
+    run.cam = cam_of(cam);
+    run.src.kind = fb ? 0u : 1u;
+    run.src.T = T;
+    run.src.tiles_x = tiles_x;
+    run.src.tile_start = tile_start;
+    run.src.tile_stride = tile_stride;
+    run.out = ho.dev;
+    run.npass = npass;
+    run.nout = nout;
+    run.nblocks0 = p0.nbf;
+    run.pass0 = p0.p0();
     // the queue order's frame (c->qorder): the framebuffer layout only. The tile layout's output index is already
     // tile-major with T-wide rows inside a tile (config 4 on one rank, 64x64 tiles: 2.019-2.025 ms per frame in that
     // order against 2.071-2.074 with the tiles re-ordered Morton inside, profiles/r03/qorder/mgpu1_*.log)
-    const uint32_t ow = layout == VHX_LAYOUT_FRAMEBUFFER ? cam->width : 0u;
-    const uint32_t oh = cam->height;
-    // a whole framebuffer frame in the default queue order: pass 0 lists its rays in that order itself (ListOrder)
-    ListOrder lo{};
-    uint64_t nb0 = nblocks;
-    bool listed = c->p0lists && npass > 1 && layout == VHX_LAYOUT_FRAMEBUFFER && T == 16 && tile_start == 0 &&
-                  tile_stride == 1 && list_order(c->qorder, cam->width, cam->height, lo, nb0);
-    if (!listed) lo = ListOrder{}, nb0 = nblocks;
-    // a tile set (the rank's share of a multi-GPU frame) under the frames-in-flight schedule lists its rays in its own
-    // block order: no flag per entry, no compaction over every entry, and the queue-state mode (ListOrder::tl)
-    if (!listed && c->p0lists && c->tile_lists && npass > 1 && layout == VHX_LAYOUT_TILES && c->qorder != 0) {
-        listed = true;
-        lo.tl = 1;
-    }
-    if (listed && (rc = ensure_lists(c, nb0))) return rc;
-    if ((listed ? nb0 * 4 : nb0) > 0x7FFFFFFFull) return fail(c, VHX_E_INVALID_ARG, "frame too large");
-    const int p0 = listed ? P0_ORDERED : P0_FLAGS;
-    const bool qm = queue_state_mode(c, listed, false, npass);
-    // shadows fuse into the ladder where pass 0 lists its rays (the list entries carry the shadow tag); a single pass
-    // or the lone frame's flag compaction traces them after the primary rays instead (below)
-    const bool fuse = shadows && listed && npass > 1;
+    run.order_w = fb ? cam->width : 0u;
+    run.order_h = cam->height;
+    run.qm = p0.qm;
+    const bool count = ho.dev.bytes != nullptr;
     // early tail (vhx_ctx::tail_*): a lone frame (the idle schedule) of a whole framebuffer on the exact path records
     // its longest rays; with a list recorded by this context's last such frame of the same size, they start now
-    const bool tail = c->tail_on && !fast && !ho.dev.bytes && !t.mips && !shadows && !listed && npass > 1 &&
-                      c->last_sched == 0 && layout == VHX_LAYOUT_FRAMEBUFFER && T == 16 && tile_start == 0 &&
-                      tile_stride == 1 && c->tail_cap > 0;
+    const bool tail = c->tail_on && !fast && !count && !t.mips && !shadows && !p0.listed && npass > 1 &&
+                      c->last_sched == 0 && whole_fb16 && c->tail_cap > 0;
     bool tail_use = false;
+    if (tail && (rc = tail_begin(c, cam->width, cam->height, nout, tail_use))) return rc;
+    PassQ q0 = pass0_q(c, npass, run.pass0, p0.qm);
+    if (tail_use) q0.skip = (const uint32_t *)c->tail_mask.ptr;  // the early tail's kernel stores them
     const uint32_t tail_blocks = (c->tail_cap + c->tail_rpw * 4u - 1u) / (c->tail_rpw * 4u);
-    if (tail) {
-        const uint64_t lbytes = (64ull + c->tail_cap) * 4ull, mbytes = ((nout + 31) / 32) * 4;
-        if ((rc = ensure(c, c->tail_list[0], lbytes)) || (rc = ensure(c, c->tail_list[1], lbytes)) ||
-            (rc = ensure(c, c->tail_mask, mbytes)))
-            return rc;
-        if (!c->tail_stream) {
-            int least = 0, greatest = 0;
-            VHX_HIP(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-            VHX_HIP(c, hipStreamCreateWithPriority(&c->tail_stream, hipStreamNonBlocking, greatest));
-            VHX_HIP(c, hipEventCreateWithFlags(&c->tail_fork, hipEventDisableTiming));
-            VHX_HIP(c, hipEventCreateWithFlags(&c->tail_join, hipEventDisableTiming));
-        }
-        uint32_t *next = (uint32_t *)c->tail_list[c->tail_cur ^ 1u].ptr;
-        VHX_HIP(c, hipMemsetAsync(next, 0, 4, c->stream));
-        tail_use = c->tail_valid && c->tail_w == cam->width && c->tail_h == cam->height;
-        if (tail_use) {
-            VHX_HIP(c, hipMemsetAsync(c->tail_mask.ptr, 0, mbytes, c->stream));
-            k_tail_mask<<<16, 256, 0, c->stream>>>((const uint32_t *)c->tail_list[c->tail_cur].ptr, c->tail_cap,
-                                                   (uint32_t)nout, (uint32_t *)c->tail_mask.ptr);
-            VHX_HIP(c, hipEventRecord(c->tail_fork, c->stream));
-            VHX_HIP(c, hipStreamWaitEvent(c->tail_stream, c->tail_fork, 0));
-        }
-        c->tail_rec = next;
-    }
-    auto launch = [&](auto bd_tag) {
+    int qrc = VHX_OK;
+    const bool bd_ok = dispatch_variant(c->tree->desc.brick_dim, t.mips != nullptr, count, p0.fuse, fast, [&](auto bd_tag, auto v) {
         constexpr int BD = decltype(bd_tag)::value;
-        PassQ q0 = pass_q(c, 0, npass, qm);
-        if (listed)
-            q0.zero = (uint32_t *)c->qctl.ptr + 16;
-        else if (npass > 1)
-            q0.flags = (uint8_t *)c->flags.ptr;
-        const unsigned g0 = (unsigned)nb0;
-        if (t.mips) {  // MIP stand-ins (no byte counting, no depth prepass: refused above)
-            k_trace_primary<false, BD, false, true><<<g0, 256, 0, c->stream>>>(
-                t, cd, ho.dev, T, tiles_x, tile_start, tile_stride, layout, bpx, bpt, q0, FastD{}, lo);
-            qrc = launch_queue_passes<false, BD, true>(c, t, cd, src, ho.dev, 1, npass, nout, nb0, p0, ow, oh, 1, qm);
-        } else if (count) {
-            k_trace_primary<true, BD><<<g0, 256, 0, c->stream>>>(
-                t, cd, ho.dev, T, tiles_x, tile_start, tile_stride, layout, bpx, bpt, q0, FastD{}, lo);
-            qrc = launch_queue_passes<true, BD>(c, t, cd, src, ho.dev, 1, npass, nout, nb0, p0, ow, oh, 1, qm);
-        } else if (fuse) {  // listed pass 0 and queue passes with the shadow continuations
-            k_trace_primary<false, BD, false, false, true><<<g0, 256, 0, c->stream>>>(
-                t, cd, ho.dev, T, tiles_x, tile_start, tile_stride, layout, bpx, bpt, q0, FastD{}, lo);
-            qrc = launch_queue_passes<false, BD, false, true>(c, t, cd, src, ho.dev, 1, npass, nout, nb0, p0, ow, oh, 1,
-                                                              qm);
-        } else {
-            if (tail_use) {  // the listed long rays first, on the second stream; pass 0 skips them
-                k_trace_tail<BD><<<tail_blocks, 256, 0, c->tail_stream>>>(
-                    t, cd, ho.dev, (const uint32_t *)c->tail_list[c->tail_cur].ptr, c->tail_rec, c->tail_cap,
-                    c->tail_min, c->tail_rpw, c->tail_prio);
-                q0.skip = (const uint32_t *)c->tail_mask.ptr;
-            }
-            if (fast)
-                k_trace_primary<false, BD, true><<<g0, 256, 0, c->stream>>>(
-                    t, cd, ho.dev, T, tiles_x, tile_start, tile_stride, layout, bpx, bpt, q0, fd, lo);
-            else
-                k_trace_primary<false, BD><<<g0, 256, 0, c->stream>>>(
-                    t, cd, ho.dev, T, tiles_x, tile_start, tile_stride, layout, bpx, bpt, q0, FastD{}, lo);
-            qrc = launch_queue_passes<false, BD>(c, t, cd, src, ho.dev, 1, npass, nout, nb0, p0, ow, oh, 1, qm);
-        }
-    };
-    const bool bd_ok = dispatch_bd(c->tree->desc.brick_dim, launch);
+        using V = decltype(v);
+        if (tail_use)  // the listed long rays first, on the second stream
+            k_trace_tail<BD><<<tail_blocks, 256, 0, c->tail_stream>>>(
+                t, run.cam, ho.dev, (const uint32_t *)c->tail_list[c->tail_cur].ptr, c->tail_rec, c->tail_cap,
+                c->tail_min, c->tail_rpw, c->tail_prio);
+        k_trace_primary<V::COUNT, BD, V::FAST, V::MIP, V::FUSE><<<(unsigned)p0.nbf, 256, 0, c->stream>>>(
+            t, run.cam, ho.dev, T, tiles_x, tile_start, tile_stride, layout, bpx, bpt, q0, fd, p0.lo);
+        qrc = launch_queue_passes<V::COUNT, BD, V::MIP, V::FUSE>(c, t, run);
+    });
     c->tail_rec = nullptr;
-    if (tail) {
-        // the frame ends with its early tail (joined before ev1 and the trace's use event); its record is next frame's
-        // list (the list it traced stays valid: an error below still leaves two well-formed lists)
-        if (tail_use) {
-            VHX_HIP(c, hipEventRecord(c->tail_join, c->tail_stream));
-            VHX_HIP(c, hipStreamWaitEvent(c->stream, c->tail_join, 0));
-        }
-        c->tail_cur ^= 1u;
-        c->tail_valid = true;
-        c->tail_w = cam->width;
-        c->tail_h = cam->height;
-    }
+    if (tail && (rc = tail_end(c, cam->width, cam->height, tail_use))) return rc;
     if (!bd_ok) return fail(c, VHX_E_INVALID_ARG, "unsupported brick_dim");
-    if (qrc) return qrc;
-    VHX_HIP(c, hipGetLastError());
-    if (c->in_prepass) return VHX_OK;  // the outer call records the end and copies its outputs
+    if ((rc = tr.end(qrc)) || c->in_prepass) return rc;  // (the prepass's outer call copies its outputs)
     // a shadow trace of this frame's hit records lists them in the same tile order (vhx_trace_shadows)
-    c->last_fb_w = layout == VHX_LAYOUT_FRAMEBUFFER ? cam->width : 0u;
-    c->last_fb_h = layout == VHX_LAYOUT_FRAMEBUFFER ? cam->height : 0u;
-    VHX_HIP(c, hipEventRecord(c->ev1, c->stream));
-    c->timed = true;
-    if ((rc = tscope.end())) return rc;  // a later write of the tree waits for this frame
-    if (shadows && !fuse) {
+    c->last_fb_w = fb ? cam->width : 0u;
+    c->last_fb_h = fb ? cam->height : 0u;
+    if (shadows && !p0.fuse) {
         // the frame's shadow rays after its primary rays (vhx_trace_shadows on the same stream); the frame's time then
         // spans both (ev0 of the primary trace, ev1 re-recorded by the shadow trace)
         c->keep_ev0 = true;
@@ -2894,24 +2057,6 @@ int vhx_trace_primary(vhx_ctx *c, const vhx_camera *cam, uint32_t T, uint32_t ti
         if (rc) return rc;
     }
     return finish_out(c, ho);
-}
-
-// The next slot of a context's pinned staging ring, sized for `bytes`: the host waits only if that slot's previous copy
-// (VHX_STAGE_SLOTS batches ago on this context) has not run yet
-static int stage_slot(vhx_ctx *c, vhx_ctx::Pinned *ring, uint32_t &next, uint64_t bytes, vhx_ctx::Pinned *&out) {
-    vhx_ctx::Pinned &P = ring[next];
-    next = (next + 1) % std::max<uint32_t>(1u, std::min(c->stage_slots, vhx_ctx::VHX_STAGE_SLOTS));
-    if (P.used) VHX_HIP(c, hipEventSynchronize(P.done));
-    if (P.bytes < bytes) {
-        if (P.ptr) VHX_HIP(c, hipHostFree(P.ptr));
-        P.ptr = nullptr;
-        P.bytes = 0;
-        VHX_HIP(c, hipHostMalloc(&P.ptr, bytes, hipHostMallocDefault));
-        P.bytes = bytes;
-    }
-    if (!P.done) VHX_HIP(c, hipEventCreateWithFlags(&P.done, hipEventDisableTiming));
-    out = &P;
-    return VHX_OK;
 }
 
 // A batch of whole frames (T == 0: vhx_trace_primary_batch) or of tile sets (T > 0: vhx_trace_tiles_batch; frame k is
@@ -2946,121 +2091,86 @@ static int trace_batch(vhx_ctx *c, const vhx_camera *cams, uint32_t n, const vhx
     // the frames are traced concurrently: two frames writing one output range would leave a result that depends on the
     // schedule instead of equalling n single-frame calls
     {
-        struct R {
-            const char *p;
-            uint64_t bytes;
-        };
-        std::vector<R> rs;
+        std::vector<MemRange> written;
         for (uint32_t k = 0; k < n; ++k) {
             const vhx_hits &o = outs[k];
             const uint64_t ent = T ? set_tiles(k) * T * T : npix;
             const void *f[7] = {o.value, o.cell, o.rgba, o.depth, o.voxel, o.impact, o.normal};
             const uint64_t w[7] = {1, 1, 1, 1, 3, 3, 3};
-            for (int j = 0; j < 7; ++j)
-                if (f[j] && ent) rs.push_back({(const char *)f[j], ent * 4 * w[j]});
+            for (int j = 0; j < 7; ++j) written.push_back({f[j], ent * 4 * w[j]});
         }
-        std::sort(rs.begin(), rs.end(), [](const R &a, const R &b) { return a.p < b.p; });
-        for (size_t i = 1; i < rs.size(); ++i)
-            if (rs[i].p < rs[i - 1].p + rs[i - 1].bytes)
-                return fail(c, VHX_E_INVALID_ARG, std::string(fn) + ": output arrays overlap each other");
+        if (ranges_meet(written, {}))
+            return fail(c, VHX_E_INVALID_ARG, std::string(fn) + ": output arrays overlap each other");
     }
     const uint32_t bx = (W + 15) / 16, by = (H + 15) / 16;
     const uint64_t nbf = T ? max_tiles * bpt : (uint64_t)bx * by, nblocks = nbf * n;
     if (nout > 0x7FFFFFFFull || nblocks > 0x7FFFFFFFull)
         return fail(c, VHX_E_INVALID_ARG, std::string(fn) + ": more than 2^31 rays in one batch");
-    VHX_HIP(c, hipSetDevice(c->device));
-    VHX_STREAM(c);
-    TraceScope tscope(c);
-    int rc = tscope.rc;
+    TraceCall tr(c);
+    int rc = tr.rc;
     if (rc) return rc;
-    if ((rc = refresh_child_rec(c))) return rc;
-    const DevTree t = dev_tree(c);
+    DevTree t;
+    if ((rc = tr.tree(t))) return rc;
     if (t.mips) return fail(c, VHX_E_INVALID_ARG, std::string(fn) + ": not available with node MIPs");
-    // the batch's cameras, outputs (and tile-set starts): packed into the next slot of the context's pinned staging ring,
-    // one copy to the device ahead of the launches on the context's stream (stage_slot: back-to-back batches on one
-    // context do not wait on the host until the ring wraps onto a copy that has not run)
+    // the batch's cameras, outputs (and tile-set starts), staged for one copy to the device
     const uint64_t cam_bytes = ((uint64_t)n * sizeof(CamD) + 255) & ~255ull;
     const uint64_t out_bytes = ((uint64_t)n * sizeof(OutD) + 255) & ~255ull;
     const uint64_t args_bytes = cam_bytes + out_bytes + (T ? (uint64_t)n * 4 : 0ull);
-    vhx_ctx::Pinned *PP = nullptr;
-    if ((rc = stage_slot(c, c->batch_pinned, c->batch_next, args_bytes, PP))) return rc;
-    vhx_ctx::Pinned &P = *PP;
-    // the device copy is read by this context's earlier batches: a stream change waits for them
-    if (c->use_recorded && c->use_stream != c->stream) VHX_HIP(c, hipStreamWaitEvent(c->stream, c->use_ev, 0));
-    if ((rc = ensure(c, c->batch_args, args_bytes))) return rc;
-    CamD *hc = (CamD *)P.ptr;
-    OutD *ho = (OutD *)((uint8_t *)P.ptr + cam_bytes);
+    vhx_ctx::Pinned *P = nullptr;
+    if ((rc = stage_acquire(c, c->batch_pinned, c->batch_next, c->batch_args, args_bytes, P))) return rc;
+    CamD *hc = (CamD *)P->ptr;
+    OutD *ho = (OutD *)((uint8_t *)P->ptr + cam_bytes);
     for (uint32_t k = 0; k < n; ++k) {
         hc[k] = cam_of(&cams[k]);
         ho[k] = OutD{outs[k].value, outs[k].cell,   outs[k].voxel, outs[k].rgba,
                      nullptr,       outs[k].impact, outs[k].normal, outs[k].depth, outs[k].shadowed};
     }
-    if (T) std::memcpy((uint8_t *)P.ptr + cam_bytes + out_bytes, starts, (size_t)n * 4);
+    if (T) std::memcpy((uint8_t *)P->ptr + cam_bytes + out_bytes, starts, (size_t)n * 4);
     uint32_t npass = 1;
     if ((rc = prepare_passes(c, nout, nblocks, npass, false, n > 1))) return rc;
-    VHX_HIP(c, hipEventRecord(c->ev0, c->stream));
-    VHX_HIP(c, hipMemcpyAsync(c->batch_args.ptr, P.ptr, args_bytes, hipMemcpyHostToDevice, c->stream));
-    VHX_HIP(c, hipEventRecord(P.done, c->stream));
-    P.used = true;
+    if ((rc = tr.start()) || (rc = stage_commit(c, *P, c->batch_args, args_bytes))) return rc;
     const CamD *dcams = (const CamD *)c->batch_args.ptr;
     const OutD *douts = (const OutD *)((const uint8_t *)c->batch_args.ptr + cam_bytes);
     const uint32_t *dstarts = T ? (const uint32_t *)((const uint8_t *)c->batch_args.ptr + cam_bytes + out_bytes) : nullptr;
-    RaySrc src{};
-    src.kind = 4u;
-    src.cams = dcams;
-    src.outs = douts;
-    src.npix = (uint32_t)npix;
-    src.T = T;
-    src.tiles_x = tiles_x;
-    src.tile_stride = stride;
-    src.starts = dstarts;
     const TileB tb{T, tiles_x, ntiles, stride, bpx, bpt};
-    const CamD cd{};
-    int qrc = VHX_OK;
     // the frames' blocks over whole tiles of the list order (k_trace_primary), or flags in the flag order; a batch of
     // tile sets lists its rays in its own block order (ListOrder::tl) or compacts flags in output-index order
-    ListOrder lo{};
-    uint64_t nbf0 = nbf;
-    bool listed = !T && c->p0lists && npass > 1 && list_order(c->qorder, W, H, lo, nbf0) && nbf0 * n * 4 <= 0x7FFFFFFFull;
-    if (!listed) lo = ListOrder{}, nbf0 = nbf;
-    if (T && c->p0lists && c->tile_lists && npass > 1 && nbf * n * 4 <= 0x7FFFFFFFull) {
-        listed = true;
-        lo.tl = 1;
-    }
-    if (listed && (rc = ensure_lists(c, nbf0 * n))) return rc;
-    const bool qm = queue_state_mode(c, listed, false, npass);
-    const bool fuse = c->shadow_on && listed && npass > 1;  // vhx_trace_primary's rule
-    auto launch = [&](auto bd_tag) {
+    Pass0Plan p0;
+    if ((rc = plan_pass0(c, npass, !T, T != 0, W, H, nbf, n, c->shadow_on, false, p0))) return rc;
+    QueueRun run;
+    run.src.kind = 4u;
+    run.src.cams = dcams;
+    run.src.outs = douts;
+    run.src.npix = (uint32_t)npix;
+    run.src.T = T;
+    run.src.tiles_x = tiles_x;
+    run.src.tile_stride = stride;
+    run.src.starts = dstarts;
+    run.npass = npass;
+    run.nout = nout;
+    run.nblocks0 = p0.nbf * n;
+    run.pass0 = p0.p0();
+    run.order_w = T ? 0u : W;
+    run.order_h = H;
+    run.frames = n;
+    run.qm = p0.qm;
+    const PassQ q0 = pass0_q(c, npass, run.pass0, p0.qm);
+    // everything the kernel would derive from the grid size, and its divisions, as constants
+    const BatchGrid bg = batch_grid((uint32_t)run.nblocks0, n, (uint32_t)p0.nbf, bx, q0, p0.lo, tb);
+    int qrc = VHX_OK;
+    const bool bd_ok = dispatch_variant(c->tree->desc.brick_dim, false, false, p0.fuse, false, [&](auto bd_tag, auto v) {
         constexpr int BD = decltype(bd_tag)::value;
-        PassQ q0 = pass_q(c, 0, npass, qm);
-        if (listed)
-            q0.zero = (uint32_t *)c->qctl.ptr + 16;
-        else if (npass > 1)
-            q0.flags = (uint8_t *)c->flags.ptr;
-        // everything the kernel would derive from the grid size, and its divisions, as constants
-        const BatchGrid bg = batch_grid((uint32_t)(nbf0 * n), n, (uint32_t)nbf0, bx, q0, lo, tb);
-        if (fuse) {
-            k_trace_primary_batch<BD, true><<<(unsigned)(nbf0 * n), 256, 0, c->stream>>>(
-                t, dcams, douts, (uint32_t)nbf0, bx, (uint32_t)npix, q0, bg, lo, tb, dstarts);
-            qrc = launch_queue_passes<false, BD, false, true>(c, t, cd, src, OutD{}, 1, npass, nout, nbf0 * n,
-                                                              P0_ORDERED, T ? 0u : W, H, n, qm);
-        } else {
-            k_trace_primary_batch<BD><<<(unsigned)(nbf0 * n), 256, 0, c->stream>>>(t, dcams, douts, (uint32_t)nbf0, bx,
-                                                                                   (uint32_t)npix, q0, bg, lo, tb, dstarts);
-            qrc = launch_queue_passes<false, BD>(c, t, cd, src, OutD{}, 1, npass, nout, nbf0 * n,
-                                                 listed ? P0_ORDERED : P0_FLAGS, T ? 0u : W, H, n, qm);
-        }
-    };
-    if (!dispatch_bd(c->tree->desc.brick_dim, launch)) return fail(c, VHX_E_INVALID_ARG, "unsupported brick_dim");
-    if (qrc) return qrc;
-    VHX_HIP(c, hipGetLastError());
+        constexpr bool FUSE = decltype(v)::FUSE;
+        k_trace_primary_batch<BD, FUSE><<<(unsigned)run.nblocks0, 256, 0, c->stream>>>(
+            t, dcams, douts, (uint32_t)p0.nbf, bx, (uint32_t)npix, q0, bg, p0.lo, tb, dstarts);
+        qrc = launch_queue_passes<false, BD, false, FUSE>(c, t, run);
+    });
+    if (!bd_ok) return fail(c, VHX_E_INVALID_ARG, "unsupported brick_dim");
+    if ((rc = tr.end(qrc))) return rc;
     // a shadow trace (or shadow batch) of these frames' hit records lists them in the same tile order
     c->last_fb_w = T ? 0u : W;
     c->last_fb_h = T ? 0u : H;
-    VHX_HIP(c, hipEventRecord(c->ev1, c->stream));
-    c->timed = true;
-    if ((rc = tscope.end())) return rc;
-    if (c->shadow_on && !fuse) {  // the frames' shadow rays after their primary rays (vhx_trace_primary's fallback)
+    if (c->shadow_on && !p0.fuse) {  // the frames' shadow rays after their primary rays (vhx_trace_primary's fallback)
         c->keep_ev0 = true;
         for (uint32_t k = 0; k < n && !rc; ++k) {
             const uint64_t ent = T ? set_tiles(k) * T * T : npix;
@@ -3082,6 +2192,7 @@ int vhx_trace_tiles_batch(vhx_ctx *c, const vhx_camera *cams, uint32_t n, uint32
     if (tile_size == 0) return c ? fail(c, VHX_E_INVALID_ARG, "vhx_trace_tiles_batch: tile_size 0") : VHX_E_INVALID_ARG;
     return trace_batch(c, cams, n, outs, tile_size, tile_starts, tile_stride, "vhx_trace_tiles_batch");
 }
+
 
 int vhx_tail_info(vhx_ctx *c, uint32_t *listed, uint32_t *width, uint32_t *height) {
     if (!c) return VHX_E_INVALID_ARG;
@@ -3106,13 +2217,11 @@ int vhx_chain_profile(vhx_ctx *c, const vhx_camera *cam, const uint32_t *pixels,
     if (n == 0) return VHX_OK;
     for (uint32_t k = 0; k < n; ++k)
         if (pixels[k] >= (uint64_t)cam->width * cam->height) return fail(c, VHX_E_INVALID_ARG, "vhx_chain_profile: pixel outside the frame");
-    VHX_HIP(c, hipSetDevice(c->device));
-    VHX_STREAM(c);
-    TraceScope tscope(c);
-    int rc = tscope.rc;
+    TraceCall tr(c);
+    int rc = tr.rc;
     if (rc) return rc;
-    if ((rc = refresh_child_rec(c))) return rc;
-    const DevTree t = dev_tree(c);
+    DevTree t;
+    if ((rc = tr.tree(t))) return rc;
     if (t.mips) return fail(c, VHX_E_INVALID_ARG, "vhx_chain_profile: not with node MIPs");
     const uint64_t pbytes = ((uint64_t)n * 4 + 255) & ~255ull, obytes = (uint64_t)n * VHX_CHAIN_WORDS * 8;
     if ((rc = ensure(c, c->scratch, pbytes + obytes))) return rc;
@@ -3128,7 +2237,7 @@ int vhx_chain_profile(vhx_ctx *c, const vhx_camera *cam, const uint32_t *pixels,
     VHX_HIP(c, hipGetLastError());
     VHX_HIP(c, hipMemcpyAsync(out, dout, obytes, hipMemcpyDeviceToHost, c->stream));
     VHX_HIP(c, hipStreamSynchronize(c->stream));
-    return tscope.end();
+    return tr.scope.end();
 #else
     return fail(c, VHX_E_STATE, "vhx_chain_profile: libvhx was built without VHX_CHAIN");
 #endif
@@ -3153,118 +2262,59 @@ int vhx_profile_counters(vhx_ctx *c, uint64_t *out, uint32_t n, int reset) {
 #endif
 }
 
-int vhx_set_shadow_light(vhx_ctx *c, const float *light) {
-    if (!c) return VHX_E_INVALID_ARG;
-    if (light && !(std::isfinite(light[0]) && std::isfinite(light[1]) && std::isfinite(light[2])))
-        return fail(c, VHX_E_INVALID_ARG, "vhx_set_shadow_light: a finite light position");
-    c->shadow_on = light != nullptr;
-    for (int k = 0; k < 3; ++k) c->shadow_light[k] = light ? light[k] : 0.0f;
-    return VHX_OK;
-}
-
-int vhx_set_depth_prepass(vhx_ctx *c, int enable, float margin) {
-    if (!c || !(margin >= 0.0f)) return VHX_E_INVALID_ARG;
-    c->prepass = enable != 0;
-    c->prepass_margin = margin;
-    return VHX_OK;
-}
-
-int vhx_set_node_mips(vhx_ctx *c, const uint32_t *node_mips, uint32_t count) {
-    if (!c) return VHX_E_INVALID_ARG;
-    if (c->shared) return fail(c, VHX_E_STATE, "vhx_set_node_mips on a shared context: set them through the owner");
-    if (!node_mips) {
-        // switching MIPs off is a tree write too: frames in flight finish with the descriptors they started with, and
-        // traces on other host threads see the switch in submission order (TreeStore ordering)
-        VHX_HIP(c, hipSetDevice(c->device));
-        VHX_STREAM(c);
-        WriteScope ws(c);
-        if (ws.rc) return ws.rc;
-        c->tree->mips_on = false;
-        return ws.end();
-    }
-    if (!c->tree->uploaded) return fail(c, VHX_E_STATE, "vhx_set_node_mips: no tree uploaded");
-    const vhx_tree_desc &d = c->tree->desc;
-    if (count != d.node_count) return fail(c, VHX_E_INVALID_ARG, "vhx_set_node_mips: count != node_count");
-    for (uint32_t i = 0; i < count; ++i) {  // every descriptor must name an uploaded brick or solid value
-        const uint32_t m = node_mips[i];
-        if (m == VHX_EMPTY) continue;
-        if ((m & VHX_SOLID_BIT) ? (m & 0x7FFFFFFFu) >= d.solid_count : m >= d.brick_count)
-            return fail(c, VHX_E_INVALID_ARG, "vhx_set_node_mips: descriptor out of range");
-    }
-    VHX_HIP(c, hipSetDevice(c->device));
-    VHX_STREAM(c);
-    WriteScope ws(c);  // frames in flight may still read the previous descriptors
-    int rc = ws.rc;
-    if (!rc && c->tree->mips.bytes < (uint64_t)count * 4) VHX_HIP(c, hipStreamSynchronize(c->stream));  // regrowth
-    if (!rc) rc = ensure(c, c->tree->mips, (uint64_t)count * 4);
-    if (rc) return rc;
-    VHX_HIP(c, hipMemcpyAsync(c->tree->mips.ptr, node_mips, (uint64_t)count * 4, hipMemcpyHostToDevice, c->stream));
-    VHX_HIP(c, hipStreamSynchronize(c->stream));
-    c->tree->mips_on = true;
-    return ws.end();
-}
-
 int vhx_trace_rays(vhx_ctx *c, const float *rays, uint64_t n, const vhx_hits *out, int on_device) {
     if (!c || !out || (!rays && n)) return VHX_E_INVALID_ARG;
     if (!c->tree->uploaded) return fail(c, VHX_E_STATE, "vhx_trace_rays before vhx_upload_tree");
     if (n == 0) return VHX_OK;
     if ((n + 255) / 256 > 0x7FFFFFFFull) return fail(c, VHX_E_INVALID_ARG, "too many rays");
-    VHX_HIP(c, hipSetDevice(c->device));
-    VHX_STREAM(c);
-    TraceScope tscope(c);
-    int rc = tscope.rc;
+    TraceCall tr(c);
+    int rc = tr.rc;
     if (rc) return rc;
     HostOut ho;
-    rc = map_out(c, out, n, on_device, ho);
-    if (rc) return rc;
+    if ((rc = map_out(c, out, n, on_device, ho))) return rc;
     const float *drays = rays;
     if (!on_device) {
         // context-owned staging buffer (a stream-ordered hipMallocAsync buffer here intermittently handed the
         // kernel stale ray data after a pageable host copy on ROCm 7.2)
-        rc = ensure(c, c->rays, n * 24);
-        if (rc) return rc;
+        if ((rc = ensure(c, c->rays, n * 24))) return rc;
         VHX_HIP(c, hipMemcpyAsync(c->rays.ptr, rays, n * 24, hipMemcpyHostToDevice, c->stream));
         drays = (const float *)c->rays.ptr;
     }
-    if ((rc = refresh_child_rec(c))) return rc;
-    const DevTree t = dev_tree(c);
+    DevTree t;
+    if ((rc = tr.tree(t))) return rc;
     if (t.mips && out->bytes)
         return fail(c, VHX_E_INVALID_ARG, "vhx_trace_rays: byte counting is not available with node MIPs");
-    uint32_t npass = 1;
-    const uint64_t nb64 = (n + 255) / 256;
-    rc = prepare_passes(c, n, nb64, npass);
-    if (rc) return rc;
-    RaySrc src{};
-    src.kind = 2u;
-    src.rays = drays;
-    CamD cd{};
-    VHX_HIP(c, hipEventRecord(c->ev0, c->stream));
-    rc = reset_passes(c, npass);
-    if (rc) return rc;
-    const bool count = ho.dev.bytes != nullptr;
-    const unsigned nb = (unsigned)((n + 255) / 256);
+    QueueRun run;
+    run.src.kind = 2u;
+    run.src.rays = drays;
+    run.out = ho.dev;
+    run.nout = n;
+    run.nblocks0 = (n + 255) / 256;
+    if ((rc = prepare_passes(c, n, run.nblocks0, run.npass))) return rc;
+    if ((rc = tr.start()) || (rc = reset_passes(c, run.npass))) return rc;
+    const PassQ q0 = pass0_q(c, run.npass, P0_LISTS);
     int qrc = VHX_OK;
-    auto launch = [&](auto bd_tag) {
+    const bool bd_ok = dispatch_variant(c->tree->desc.brick_dim, t.mips != nullptr, ho.dev.bytes != nullptr, false, false,
+                                        [&](auto bd_tag, auto v) {
         constexpr int BD = decltype(bd_tag)::value;
-        const PassQ q0 = pass_q(c, 0, npass);
-        if (t.mips) {
-            k_trace_rays<false, BD, true><<<nb, 256, 0, c->stream>>>(t, drays, n, ho.dev, q0);
-            qrc = launch_queue_passes<false, BD, true>(c, t, cd, src, ho.dev, 1, npass, n, nb64);
-        } else if (count) {
-            k_trace_rays<true, BD><<<nb, 256, 0, c->stream>>>(t, drays, n, ho.dev, q0);
-            qrc = launch_queue_passes<true, BD>(c, t, cd, src, ho.dev, 1, npass, n, nb64);
-        } else {
-            k_trace_rays<false, BD><<<nb, 256, 0, c->stream>>>(t, drays, n, ho.dev, q0);
-            qrc = launch_queue_passes<false, BD>(c, t, cd, src, ho.dev, 1, npass, n, nb64);
-        }
-    };
-    if (!dispatch_bd(c->tree->desc.brick_dim, launch)) return fail(c, VHX_E_INVALID_ARG, "unsupported brick_dim");
-    if (qrc) return qrc;
-    VHX_HIP(c, hipGetLastError());
-    VHX_HIP(c, hipEventRecord(c->ev1, c->stream));
-    c->timed = true;
-    if ((rc = tscope.end())) return rc;
+        using V = decltype(v);
+        k_trace_rays<V::COUNT, BD, V::MIP><<<(unsigned)run.nblocks0, 256, 0, c->stream>>>(t, drays, n, ho.dev, q0);
+        qrc = launch_queue_passes<V::COUNT, BD, V::MIP, V::FUSE>(c, t, run);
+    });
+    if (!bd_ok) return fail(c, VHX_E_INVALID_ARG, "unsupported brick_dim");
+    if ((rc = tr.end(qrc))) return rc;
     return finish_out(c, ho);
+}
+
+// The flag order of a shadow trace over `frames` frames of n hit records each: when n is the pixel count of this
+// context's last framebuffer frame, the tile order of c->qorder (any order is a permutation of 0..n-1, so the records
+// need not even be that frame's for the result to be exact), else output-index order. npos: the positions to scan.
+static FlagOrder shadow_order(const vhx_ctx *c, uint64_t n, uint32_t frames, uint64_t &npos) {
+    const bool fb = c->last_fb_w && (uint64_t)c->last_fb_w * c->last_fb_h == n;
+    npos = n * frames;
+    const FlagOrder ord = flag_order(fb ? c->qorder : 0u, c->last_fb_w, c->last_fb_h, npos, frames);
+    if (!ord.W) npos = n * frames;
+    return ord;
 }
 
 int vhx_trace_shadows(vhx_ctx *c, const float light[3], uint64_t n, const uint32_t *value, const float *impact,
@@ -3275,87 +2325,48 @@ int vhx_trace_shadows(vhx_ctx *c, const float light[3], uint64_t n, const uint32
     if (n >= 0x7FFFFFFFull) return fail(c, VHX_E_INVALID_ARG, "too many rays");
     // the outputs are written while the hit records are still being read (the flags are cleared by the compaction
     // kernel that reads value[]): they must not overlap them or each other
-    {
-        struct R {
-            const void *p;
-            uint64_t bytes;
-        } outs[] = {{shadowed, n * 4}, {rgba, n * 4}, {bytes, n * 4}},
-          ins[] = {{value, n * 4}, {impact, n * 12}, {normal, n * 12}};
-        auto overlap = [](const R &a, const R &b) {
-            return a.p && b.p && (const char *)a.p < (const char *)b.p + b.bytes &&
-                   (const char *)b.p < (const char *)a.p + a.bytes;
-        };
-        for (int i = 0; i < 3; ++i) {
-            for (int j = 0; j < 3; ++j)
-                if (overlap(outs[i], ins[j]))
-                    return fail(c, VHX_E_INVALID_ARG, "vhx_trace_shadows: an output overlaps the hit records");
-            for (int j = i + 1; j < 3; ++j)
-                if (overlap(outs[i], outs[j]))
-                    return fail(c, VHX_E_INVALID_ARG, "vhx_trace_shadows: outputs overlap each other");
-        }
-    }
-    VHX_HIP(c, hipSetDevice(c->device));
-    VHX_STREAM(c);
-    TraceScope tscope(c);
-    int rc = tscope.rc;
+    const int meet = ranges_meet({{shadowed, n * 4}, {rgba, n * 4}, {bytes, n * 4}},
+                                 {{value, n * 4}, {impact, n * 12}, {normal, n * 12}});
+    if (meet == 1) return fail(c, VHX_E_INVALID_ARG, "vhx_trace_shadows: an output overlaps the hit records");
+    if (meet == 2) return fail(c, VHX_E_INVALID_ARG, "vhx_trace_shadows: outputs overlap each other");
+    TraceCall tr(c);
+    int rc = tr.rc;
     if (rc) return rc;
-    uint32_t npass = 1;
-    const uint64_t nb64 = (n + 255) / 256;
-    rc = prepare_passes(c, n, nb64, npass, true);
-    if (rc) return rc;
-    if ((rc = refresh_child_rec(c))) return rc;
-    const DevTree t = dev_tree(c);
+    QueueRun run;
+    run.first = 0;
+    run.nout = n;
+    run.nblocks0 = (n + 255) / 256;
+    if ((rc = prepare_passes(c, n, run.nblocks0, run.npass, true))) return rc;
+    DevTree t;
+    if ((rc = tr.tree(t))) return rc;
     if (t.mips && bytes)
         return fail(c, VHX_E_INVALID_ARG, "vhx_trace_shadows: byte counting is not available with node MIPs");
-    RaySrc src{};
-    src.kind = 3u;
-    src.impact = impact;
-    src.normal = normal;
-    src.lx = light[0];
-    src.ly = light[1];
-    src.lz = light[2];
-    OutD so{};
-    so.value = shadowed;
-    so.rgba = rgba;
-    so.bytes = bytes;
-    CamD cd{};
-    if (!c->keep_ev0) VHX_HIP(c, hipEventRecord(c->ev0, c->stream));  // (a fused-shadow fallback keeps the primary's)
+    run.src.kind = 3u;
+    run.src.impact = impact;
+    run.src.normal = normal;
+    run.src.lx = light[0];
+    run.src.ly = light[1];
+    run.src.lz = light[2];
+    run.out.value = shadowed;
+    run.out.rgba = rgba;
+    run.out.bytes = bytes;
+    run.qm = queue_state_mode(c, false, true, run.npass);
+    if ((rc = tr.start())) return rc;
     // no reset_passes: the hit compaction (k_count_flags) zeroes the queue passes' counters
     if (bytes) VHX_HIP(c, hipMemsetAsync(bytes, 0, n * 4, c->stream));
-    // wave-dense secondary rays: the hit pixels, in frame order, are pass 0's queue
-    // (when n is the pixel count of this context's last framebuffer frame, in the tile order of c->qorder: any
-    // order is a permutation of 0..n-1, so the records need not even be that frame's for the result to be exact)
-    {
-        uint64_t npos = n;
-        const bool fb = c->last_fb_w && (uint64_t)c->last_fb_w * c->last_fb_h == n;
-        const FlagOrder ord = flag_order(fb ? c->qorder : 0u, c->last_fb_w, c->last_fb_h, npos);
-        const unsigned nb = (unsigned)((npos + 1023) / 1024);
-        uint32_t *counts = (uint32_t *)c->counts.ptr, *offsets = (uint32_t *)c->offsets.ptr;
-        k_count_flags<true><<<nb, 256, 0, c->stream>>>(value, npos, counts, (uint32_t *)c->qctl.ptr + 16, shadowed,
-                                                       ord, n);
-        launch_scan(c, counts, nb, nullptr, 1, offsets, (uint32_t *)c->qctl.ptr + 7, nb);
-        k_emit_flags<true><<<nb, 256, 0, c->stream>>>(value, npos, offsets, (uint32_t *)c->queue[1].ptr, ord);
-        VHX_HIP(c, hipGetLastError());
-    }
+    // wave-dense secondary rays: the hit pixels, in the frame's queue order, are pass 0's queue
+    uint64_t npos = 0;
+    const FlagOrder ord = shadow_order(c, n, 1, npos);
+    if ((rc = compact_flags<true>(c, value, npos, ord, (uint32_t *)c->qctl.ptr + 7, (uint32_t *)c->queue[1].ptr, shadowed, n)))
+        return rc;
     int qrc = VHX_OK;
-    auto launch = [&](auto bd_tag) {
-        constexpr int BD = decltype(bd_tag)::value;
-        if (t.mips)
-            qrc = launch_queue_passes<false, BD, true>(c, t, cd, src, so, 0, npass, n, nb64, P0_LISTS, 0, 0, 1,
-                                                     queue_state_mode(c, false, true, npass));
-        else if (bytes)
-            qrc = launch_queue_passes<true, BD>(c, t, cd, src, so, 0, npass, n, nb64, P0_LISTS, 0, 0, 1,
-                                                     queue_state_mode(c, false, true, npass));
-        else
-            qrc = launch_queue_passes<false, BD>(c, t, cd, src, so, 0, npass, n, nb64, P0_LISTS, 0, 0, 1,
-                                                     queue_state_mode(c, false, true, npass));
-    };
-    if (!dispatch_bd(c->tree->desc.brick_dim, launch)) return fail(c, VHX_E_INVALID_ARG, "unsupported brick_dim");
-    if (qrc) return qrc;
-    VHX_HIP(c, hipGetLastError());
-    VHX_HIP(c, hipEventRecord(c->ev1, c->stream));
-    c->timed = true;
-    return tscope.end();
+    const bool bd_ok = dispatch_variant(c->tree->desc.brick_dim, t.mips != nullptr, bytes != nullptr, false, false,
+                                        [&](auto bd_tag, auto v) {
+        using V = decltype(v);
+        qrc = launch_queue_passes<V::COUNT, decltype(bd_tag)::value, V::MIP, V::FUSE>(c, t, run);
+    });
+    if (!bd_ok) return fail(c, VHX_E_INVALID_ARG, "unsupported brick_dim");
+    return tr.end(qrc);
 }
 
 int vhx_trace_shadows_batch(vhx_ctx *c, const float light[3], uint32_t nf, uint64_t n, const vhx_shadow_frame *frames) {
@@ -3367,126 +2378,67 @@ int vhx_trace_shadows_batch(vhx_ctx *c, const float light[3], uint32_t nf, uint6
     const uint64_t ntot = n * nf;
     // every frame's outputs are written while every frame's hit records are read: no overlaps anywhere in the batch
     {
-        struct R {
-            const void *p;
-            uint64_t bytes;
-        };
-        std::vector<R> outs, ins;
+        std::vector<MemRange> outs, ins;
         for (uint32_t k = 0; k < nf; ++k) {
             const vhx_shadow_frame &f = frames[k];
             if (!f.value || !f.impact || !f.normal || !f.shadowed)
                 return fail(c, VHX_E_INVALID_ARG, "vhx_trace_shadows_batch: a frame lacks value, impact, normal or shadowed");
             outs.push_back({f.shadowed, n * 4});
-            if (f.rgba) outs.push_back({f.rgba, n * 4});
+            outs.push_back({f.rgba, n * 4});
             ins.push_back({f.value, n * 4});
             ins.push_back({f.impact, n * 12});
             ins.push_back({f.normal, n * 12});
         }
-        auto overlap = [](const R &a, const R &b) {
-            return (const char *)a.p < (const char *)b.p + b.bytes && (const char *)b.p < (const char *)a.p + a.bytes;
-        };
-        for (size_t i = 0; i < outs.size(); ++i) {
-            for (const R &in : ins)
-                if (overlap(outs[i], in))
-                    return fail(c, VHX_E_INVALID_ARG, "vhx_trace_shadows_batch: an output overlaps the hit records");
-            for (size_t j = i + 1; j < outs.size(); ++j)
-                if (overlap(outs[i], outs[j]))
-                    return fail(c, VHX_E_INVALID_ARG, "vhx_trace_shadows_batch: outputs overlap each other");
-        }
+        const int meet = ranges_meet(outs, ins);
+        if (meet == 1) return fail(c, VHX_E_INVALID_ARG, "vhx_trace_shadows_batch: an output overlaps the hit records");
+        if (meet == 2) return fail(c, VHX_E_INVALID_ARG, "vhx_trace_shadows_batch: outputs overlap each other");
     }
-    VHX_HIP(c, hipSetDevice(c->device));
-    VHX_STREAM(c);
-    TraceScope tscope(c);
-    int rc = tscope.rc;
+    TraceCall tr(c);
+    int rc = tr.rc;
     if (rc) return rc;
-    if ((rc = refresh_child_rec(c))) return rc;
-    const DevTree t = dev_tree(c);
+    DevTree t;
+    if ((rc = tr.tree(t))) return rc;
     if (t.mips) return fail(c, VHX_E_INVALID_ARG, "vhx_trace_shadows_batch: not available with node MIPs");
-    uint32_t npass = 1;
-    const uint64_t nb64 = (ntot + 255) / 256;
-    if ((rc = prepare_passes(c, ntot, nb64, npass, true, nf > 1))) return rc;
+    QueueRun run;
+    run.first = 0;
+    run.nout = ntot;
+    run.nblocks0 = (ntot + 255) / 256;
+    run.frames = nf;
+    if ((rc = prepare_passes(c, ntot, run.nblocks0, run.npass, true, nf > 1))) return rc;
     // the frames' ShD records, then their value pointers (FlagOrder::fvals), staged like vhx_trace_primary_batch's
     const uint64_t sh_bytes = ((uint64_t)nf * sizeof(ShD) + 255) & ~255ull, args_bytes = sh_bytes + (uint64_t)nf * 8;
-    vhx_ctx::Pinned *PP = nullptr;
-    if ((rc = stage_slot(c, c->shadow_pinned, c->shadow_next, args_bytes, PP))) return rc;
-    vhx_ctx::Pinned &P = *PP;
-    if (c->use_recorded && c->use_stream != c->stream) VHX_HIP(c, hipStreamWaitEvent(c->stream, c->use_ev, 0));
-    if ((rc = ensure(c, c->shadow_args, args_bytes))) return rc;
-    ShD *hs = (ShD *)P.ptr;
-    uint64_t *hv = (uint64_t *)((uint8_t *)P.ptr + sh_bytes);
+    vhx_ctx::Pinned *P = nullptr;
+    if ((rc = stage_acquire(c, c->shadow_pinned, c->shadow_next, c->shadow_args, args_bytes, P))) return rc;
+    ShD *hs = (ShD *)P->ptr;
+    uint64_t *hv = (uint64_t *)((uint8_t *)P->ptr + sh_bytes);
     for (uint32_t k = 0; k < nf; ++k) {
         hs[k] = ShD{frames[k].value, frames[k].impact, frames[k].normal, frames[k].shadowed, frames[k].rgba};
         hv[k] = (uint64_t)(uintptr_t)frames[k].value;
     }
-    VHX_HIP(c, hipEventRecord(c->ev0, c->stream));
-    VHX_HIP(c, hipMemcpyAsync(c->shadow_args.ptr, P.ptr, args_bytes, hipMemcpyHostToDevice, c->stream));
-    VHX_HIP(c, hipEventRecord(P.done, c->stream));
-    P.used = true;
+    if ((rc = tr.start()) || (rc = stage_commit(c, *P, c->shadow_args, args_bytes))) return rc;
     // shadowed = 0 where no shadow ray is cast (vhx_trace_shadows clears inside its count kernel)
     for (uint32_t k = 0; k < nf; ++k) VHX_HIP(c, hipMemsetAsync(frames[k].shadowed, 0, n * 4, c->stream));
-    RaySrc src{};
-    src.kind = 5u;
-    src.lx = light[0];
-    src.ly = light[1];
-    src.lz = light[2];
-    src.npix = (uint32_t)n;
-    src.shs = (const ShD *)c->shadow_args.ptr;
-    {
-        // every frame's hit records in the tile order of the frames they came from (c->last_fb_*), frame by frame
-        uint64_t npos = ntot;
-        const bool fb = c->last_fb_w && (uint64_t)c->last_fb_w * c->last_fb_h == n;
-        FlagOrder ord = flag_order(fb ? c->qorder : 0u, c->last_fb_w, c->last_fb_h, npos, nf);
-        if (!ord.W) npos = ntot;
-        ord.fpix = n;
-        ord.fvals = (const uint64_t *)((const uint8_t *)c->shadow_args.ptr + sh_bytes);
-        const unsigned nb = (unsigned)((npos + 1023) / 1024);
-        uint32_t *counts = (uint32_t *)c->counts.ptr, *offsets = (uint32_t *)c->offsets.ptr;
-        if ((uint64_t)nb * 4 > c->counts.bytes || (uint64_t)nb * 4 > c->offsets.bytes) {
-            if ((rc = ensure_lists(c, nb))) return rc;
-            counts = (uint32_t *)c->counts.ptr;
-            offsets = (uint32_t *)c->offsets.ptr;
-        }
-        k_count_flags<true><<<nb, 256, 0, c->stream>>>(nullptr, npos, counts, (uint32_t *)c->qctl.ptr + 16, nullptr, ord);
-        launch_scan(c, counts, nb, nullptr, 1, offsets, (uint32_t *)c->qctl.ptr + 7, nb);
-        k_emit_flags<true><<<nb, 256, 0, c->stream>>>(nullptr, npos, offsets, (uint32_t *)c->queue[1].ptr, ord);
-        VHX_HIP(c, hipGetLastError());
-    }
+    run.src.kind = 5u;
+    run.src.lx = light[0];
+    run.src.ly = light[1];
+    run.src.lz = light[2];
+    run.src.npix = (uint32_t)n;
+    run.src.shs = (const ShD *)c->shadow_args.ptr;
+    run.qm = queue_state_mode(c, false, true, run.npass);
+    // every frame's hit records in the tile order of the frames they came from (c->last_fb_*), frame by frame
+    uint64_t npos = 0;
+    FlagOrder ord = shadow_order(c, n, nf, npos);
+    ord.fpix = n;
+    ord.fvals = (const uint64_t *)((const uint8_t *)c->shadow_args.ptr + sh_bytes);
+    if ((rc = compact_flags<true>(c, nullptr, npos, ord, (uint32_t *)c->qctl.ptr + 7, (uint32_t *)c->queue[1].ptr)))
+        return rc;
     int qrc = VHX_OK;
-    const CamD cd{};
-    auto launch = [&](auto bd_tag) {
-        constexpr int BD = decltype(bd_tag)::value;
-        qrc = launch_queue_passes<false, BD>(c, t, cd, src, OutD{}, 0, npass, ntot, nb64, P0_LISTS, 0, 0, nf,
-                                             queue_state_mode(c, false, true, npass));
-    };
-    if (!dispatch_bd(c->tree->desc.brick_dim, launch)) return fail(c, VHX_E_INVALID_ARG, "unsupported brick_dim");
-    if (qrc) return qrc;
-    VHX_HIP(c, hipGetLastError());
-    VHX_HIP(c, hipEventRecord(c->ev1, c->stream));
-    c->timed = true;
-    return tscope.end();
+    const bool bd_ok = dispatch_bd(c->tree->desc.brick_dim, [&](auto bd_tag) {
+        qrc = launch_queue_passes<false, decltype(bd_tag)::value>(c, t, run);
+    });
+    if (!bd_ok) return fail(c, VHX_E_INVALID_ARG, "unsupported brick_dim");
+    return tr.end(qrc);
 }
 
-int vhx_untile_frame(vhx_ctx *c, const void *gathered, uint32_t planes, uint32_t ranks, uint32_t tiles_per_rank,
-                     uint32_t T, uint32_t width, uint32_t height, uint32_t *fb_rgba, float *fb_depth) {
-    if (!c || !gathered || (!fb_rgba && !fb_depth) || planes < 1 || planes > 2 || (planes == 1 && fb_depth) ||
-        ranks == 0 || T == 0 || width == 0 || height == 0)
-        return fail(c, VHX_E_INVALID_ARG, "vhx_untile_frame: bad arguments");
-    const uint32_t tiles_x = (width + T - 1) / T, tiles_y = (height + T - 1) / T;
-    const uint64_t ntiles = (uint64_t)tiles_x * tiles_y;
-    if (ntiles > 0xFFFFFFFFull || (uint64_t)tiles_per_rank * ranks < ntiles)
-        return fail(c, VHX_E_INVALID_ARG, "vhx_untile_frame: tiles_per_rank * ranks does not cover the frame");
-    const uint64_t n = (uint64_t)ranks * planes * tiles_per_rank * T * T;
-    if ((n + 255) / 256 > 0x7FFFFFFFull) return fail(c, VHX_E_INVALID_ARG, "too many pixels");
-    VHX_HIP(c, hipSetDevice(c->device));
-    VHX_STREAM(c);
-    return launch_untile(c, c->stream, gathered, planes, ranks, tiles_per_rank, T, width, height, fb_rgba, fb_depth);
-}
-
-int vhx_untile_rgba(vhx_ctx *c, const uint32_t *gathered, uint32_t ranks, uint32_t tiles_per_rank, uint32_t T,
-                    uint32_t width, uint32_t height, uint32_t *fb, int on_device) {
-    if (!c || !gathered || !fb || ranks == 0 || T == 0 || width == 0 || height == 0) return VHX_E_INVALID_ARG;
-    if (!on_device) return fail(c, VHX_E_INVALID_ARG, "vhx_untile_rgba works on device buffers");
-    return vhx_untile_frame(c, gathered, 1, ranks, tiles_per_rank, T, width, height, fb, nullptr);
-}
 
 }  // extern "C"
