@@ -231,7 +231,7 @@ void vhx_destroy(vhx_ctx *c) {
                       &c->flags, &c->qargs, &c->state, &c->stateq, &c->upd, &c->prepass_depth, &c->batch_args, &c->scan_part,
                       &c->shadow_args, &c->tail_list[0], &c->tail_list[1], &c->tail_mask, &c->build.occ, &c->build.rank,
                       &c->build.first, &c->build.part, &c->build.table, &c->build.ctl, &c->build.grid,
-                      &c->build.simp})
+                      &c->build.simp, &c->sky})
         if (b->ptr) (void)hipFree(b->ptr);
     if (c->tail_stream) {
         (void)hipStreamSynchronize(c->tail_stream);
@@ -346,6 +346,9 @@ static int apply_tuning(vhx_ctx *c, const std::string &key, const std::string &v
     } else if (key == "finter") {  // batches: pass-0 blocks of the frames interleaved (1) or frame-major (0)
         if (!parse_u32(val, x) || x > 1) return bad();
         c->frame_interleave = x != 0;
+    } else if (key == "skyblocks") {  // batches: all-sky blocks classified ahead of pass 0 (1) or every block alike (0)
+        if (!parse_u32(val, x) || x > 1) return bad();
+        c->skyblocks = x != 0;
     } else if (key == "stage_slots") {  // batch staging ring slots in use (1 = wait for the previous batch's copy)
         if (!parse_u32(val, x) || x == 0 || x > vhx_ctx::VHX_STAGE_SLOTS) return bad();
         c->stage_slots = x;
@@ -523,6 +526,7 @@ void vhx::copy_sched(vhx_ctx *c, const vhx_ctx *owner) {
     c->shadow_budget = owner->shadow_budget;
     c->stage_slots = owner->stage_slots;
     c->frame_interleave = owner->frame_interleave;
+    c->skyblocks = owner->skyblocks;
     c->tail_on = owner->tail_on;
     c->tail_min = owner->tail_min;
     c->tail_rpw = owner->tail_rpw;

@@ -6,6 +6,7 @@
 //                    (examples/gpu_render.rs:196-257, benches/performance.rs:29-66) traced with get_by_ray semantics
 //                    (src/raytracing/cpu.rs:296-458); replaces the WGSL `update` kernel dispatched by
 //                    VhxRenderNode::run (src/raytracing/bevy/pipeline/mod.rs:96-155)
+//   k_classify_sky   a batch's sky mask: the 16x16 blocks whose every pixel misses the root cube (skyblock.hpp)
 //   k_trace_rays     pass 0 of an explicit ray batch (BoxTree::get_by_ray over many rays)
 //   k_trace_queue    the queue passes: the rays an earlier pass abandoned at its step budget, and shadow rays
 //   k_trace_tail, k_tail_mask  the early tail of a lone frame
@@ -25,6 +26,9 @@
 
 #include "../../include/vhx.h"
 #include "trace.hpp"
+#define VHX_SKY_FN __host__ __device__
+#include "skyblock.hpp"
+static_assert(VHX_RAY_GLASS == 1u, "skyblock.hpp spells the glass model's number out (it includes no header)");
 
 using namespace vhx;
 
@@ -135,6 +139,24 @@ __device__ __forceinline__ bool glass_clear_miss(const CamD &c, uint32_t px, uin
     if (!safe || !__builtin_isfinite(tmin) || !__builtin_isfinite(tmax)) return false;
     const float m = 1e-5f * __builtin_fmaxf(__builtin_fabsf(tmin), __builtin_fabsf(tmax));
     return tmax < -m || tmin - tmax > m;
+}
+
+// The sky mask of a batch's pass 0 (vhx_ctx::skyblocks): one thread per (frame, 16x16 block), block_is_sky
+// (skyblock.hpp) on the block's pixels inside the frame; mask[f * blocks_x * blocks_y + by * blocks_x + bx] = 1 where
+// every pixel of the block misses the root cube on the exact path. A byte per block: k_trace_primary_batch reads its
+// entry's word with a scalar load.
+__global__ void __launch_bounds__(256) k_classify_sky(const CamD *__restrict__ cams, uint32_t nfr, uint32_t blocks_x,
+                                                      uint32_t blocks_y, uint32_t tree_size,
+                                                      uint8_t *__restrict__ mask) {
+    const uint32_t nb = blocks_x * blocks_y;
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= nfr * nb) return;
+    const uint32_t f = i / nb, b = i - f * nb, by = b / blocks_x, bx = b - by * blocks_x;
+    const CamD &c = cams[f];
+    const SkyCam s{c.model, c.width, c.height, {c.ox, c.oy, c.oz}, {c.blx, c.bly, c.blz}, {c.rx, c.ry, c.rz},
+                   {c.ux, c.uy, c.uz}, c.pw, c.ph};
+    const uint32_t x1 = min(bx * 16u + 15u, c.width - 1u), y1 = min(by * 16u + 15u, c.height - 1u);
+    mask[i] = block_is_sky(s, tree_size, bx * 16u, by * 16u, x1, y1) ? 1 : 0;
 }
 
 // ------------------------------------------------------------------------------------------- multi-pass scheduling
@@ -839,6 +861,8 @@ struct BatchGrid {
     UDiv split;       // workgroup -> (frame, frame block): by nfr (interleaved) or by nblocks_frame (frame-major)
     UDiv ltx, bx;     // frame block -> block coordinates: by lo.tx (list order) or by blocks_x (row-major)
     UDiv bpt, bpx, tiles_x;  // tile sets: by TileB's bpt, bpx and tiles_x
+    // sky blocks (the kernel's `sky` mask, k_classify_sky): the frame's 16x16 raster blocks and the frames' common size
+    uint32_t sbx, sby, W, H;
 };
 static BatchGrid batch_grid(uint32_t nblocks, uint32_t nfr, uint32_t nblocks_frame, uint32_t blocks_x, const PassQ &q,
                             const ListOrder &lo, const TileB &tb) {
@@ -891,20 +915,61 @@ __global__ void __launch_bounds__(256) VHX_BATCH_ATTR k_trace_primary_batch(DevT
                                                              const OutD *__restrict__ outs, uint32_t nblocks_frame,
                                                              uint32_t blocks_x, uint32_t npix, PassQ q, BatchGrid bg,
                                                              ListOrder lo = ListOrder{}, TileB tb = TileB{},
-                                                             const uint32_t *__restrict__ starts = nullptr) {
+                                                             const uint32_t *__restrict__ starts = nullptr,
+                                                             const uint32_t *__restrict__ sky = nullptr) {
     __shared__ uint64_t occ_tab[OCC_TAB_WORDS];
-    fill_occ_tab(occ_tab);
     zero_ctl(q.zero);
-    __syncthreads();
     const uint32_t bid = __builtin_amdgcn_readfirstlane(xcd_block(blockIdx.x, q.xcd_group, bg));
     // frame-major (all of frame 0's blocks, then frame 1's, ...) or interleaved (block sb of every frame in turn: the
     // frames' rays through one screen region run together and share the caches)
     const uint32_t bq = udiv(bid, bg.split);
     const uint32_t f = __builtin_amdgcn_readfirstlane(q.finter ? bid - bq * bg.nfr : bq);
     const uint32_t sb = __builtin_amdgcn_readfirstlane(q.finter ? bq : bid - bq * nblocks_frame);
-    const CamD cam = cams[f];
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
-    uint32_t px, py, local;
+    uint32_t px = 0, py = 0, local;
+    if (!tb.T) {
+        uint32_t bx, by;
+        if (lo.tx) {  // this frame's blocks in list order (k_trace_primary)
+            list_block(lo, bg.ltx, sb, bx, by);
+            px = bx * 16u + (wave & 1u) * 8u + compact_bits(lane);
+            py = by * 16u + (wave >> 1) * 8u + compact_bits(lane >> 1);
+        } else {
+            by = udiv(sb, bg.bx);
+            bx = sb - by * blocks_x;
+            px = bx * 16u + (wave & 1u) * 8u + (lane & 7u);
+            py = by * 16u + (wave >> 1) * 8u + (lane >> 3);
+        }
+        // Sky blocks (vhx_ctx::skyblocks; whole frames without fused shadows -- tile sets and the FUSE instantiations
+        // keep the full path for every block): a block that k_classify_sky marked, or a block of the list order's
+        // padding past the frame, holds no ray that enters the tree. Its workgroup writes the miss record of every pixel
+        // through the same store() and its flags or empty lists, and ends: no occupancy table, no barrier, no camera, no
+        // per-lane sky test. The branch is workgroup-uniform (scalar), ahead of the only barrier. The block's mask word
+        // and outs[f] are read together, so the wave waits for one scalar round trip (the empty asm keeps the compiler
+        // from moving the second load behind the branch; a tree block drops the pointers again).
+        if (!FUSE && sky) {
+            const bool inside = bx < bg.sbx && by < bg.sby;
+            const uint32_t mi = inside ? f * (bg.sbx * bg.sby) + by * bg.sbx + bx : 0u;
+            const uint32_t word = sky[mi >> 2];
+            const OutD out = outs[f];
+            asm volatile("" ::"s"(word), "s"(out.value), "s"(out.cell), "s"(out.voxel), "s"(out.rgba), "s"(out.impact),
+                         "s"(out.normal), "s"(out.depth));
+            if (!inside || ((word >> ((mi & 3u) * 8u)) & 1u) != 0u) {
+                local = py * bg.W + px;
+                if (px < bg.W && py < bg.H) {
+                    HitOut h;
+                    h.hit = false;
+                    h.bytes = 0;
+                    store(t, out, local, mk(0.0f, 0.0f, 0.0f), h);
+                    if (q.flags) q.flags[(uint64_t)f * npix + local] = 0;
+                }
+                if ((lo.tx || lo.tl) && q.tmp) wave_append(false, 0u, q.tmp, q.counts, bid * 4u + wave);
+                return;
+            }
+        }
+    }
+    fill_occ_tab(occ_tab);
+    __syncthreads();
+    const CamD cam = cams[f];
     bool valid, entry;  // entry: the position has an output entry (its flag is written)
     if (tb.T) {
         const uint32_t j = __builtin_amdgcn_readfirstlane(udiv(sb, bg.bpt)), sbb = sb - j * tb.bpt;
@@ -920,16 +985,6 @@ __global__ void __launch_bounds__(256) VHX_BATCH_ATTR k_trace_primary_batch(DevT
         valid = entry && tile < tb.ntiles && px < cam.width && py < cam.height;
         local = (j * tb.T + ly) * tb.T + lx;
     } else {
-        if (lo.tx) {  // this frame's blocks in list order (k_trace_primary)
-            uint32_t bx, by;
-            list_block(lo, bg.ltx, sb, bx, by);
-            px = bx * 16u + (wave & 1u) * 8u + compact_bits(lane);
-            py = by * 16u + (wave >> 1) * 8u + compact_bits(lane >> 1);
-        } else {
-            const uint32_t sby = udiv(sb, bg.bx);
-            px = (sb - sby * blocks_x) * 16u + (wave & 1u) * 8u + (lane & 7u);
-            py = sby * 16u + (wave >> 1) * 8u + (lane >> 3);
-        }
         valid = entry = px < cam.width && py < cam.height;
         local = py * cam.width + px;
     }
@@ -2128,6 +2183,10 @@ static int trace_batch(vhx_ctx *c, const vhx_camera *cams, uint32_t n, const vhx
     if (T) std::memcpy((uint8_t *)P->ptr + cam_bytes + out_bytes, starts, (size_t)n * 4);
     uint32_t npass = 1;
     if ((rc = prepare_passes(c, nout, nblocks, npass, false, n > 1))) return rc;
+    // the sky mask: a byte per frame and raster block, read by words (grown only when a larger batch comes: sized here,
+    // ahead of the launches, like every other per-trace buffer)
+    const bool sky = c->skyblocks && !T;
+    if (sky && (rc = ensure(c, c->sky, ((uint64_t)bx * by * n + 3) & ~3ull))) return rc;
     if ((rc = tr.start()) || (rc = stage_commit(c, *P, c->batch_args, args_bytes))) return rc;
     const CamD *dcams = (const CamD *)c->batch_args.ptr;
     const OutD *douts = (const OutD *)((const uint8_t *)c->batch_args.ptr + cam_bytes);
@@ -2156,13 +2215,23 @@ static int trace_batch(vhx_ctx *c, const vhx_camera *cams, uint32_t n, const vhx
     run.qm = p0.qm;
     const PassQ q0 = pass0_q(c, npass, run.pass0, p0.qm);
     // everything the kernel would derive from the grid size, and its divisions, as constants
-    const BatchGrid bg = batch_grid((uint32_t)run.nblocks0, n, (uint32_t)p0.nbf, bx, q0, p0.lo, tb);
+    BatchGrid bg = batch_grid((uint32_t)run.nblocks0, n, (uint32_t)p0.nbf, bx, q0, p0.lo, tb);
+    const uint32_t *dsky = nullptr;  // null: every block takes the full path
+    if (sky && !p0.fuse) {  // one launch per batch, ahead of pass 0 on the same stream (the FUSE kernels do not read it)
+        const uint32_t nsky = bx * by * n;
+        k_classify_sky<<<(nsky + 255u) / 256u, 256, 0, c->stream>>>(dcams, n, bx, by, t.size, (uint8_t *)c->sky.ptr);
+        dsky = (const uint32_t *)c->sky.ptr;
+        bg.sbx = bx;
+        bg.sby = by;
+        bg.W = W;
+        bg.H = H;
+    }
     int qrc = VHX_OK;
     const bool bd_ok = dispatch_variant(c->tree->desc.brick_dim, false, false, p0.fuse, false, [&](auto bd_tag, auto v) {
         constexpr int BD = decltype(bd_tag)::value;
         constexpr bool FUSE = decltype(v)::FUSE;
         k_trace_primary_batch<BD, FUSE><<<(unsigned)run.nblocks0, 256, 0, c->stream>>>(
-            t, dcams, douts, (uint32_t)p0.nbf, bx, (uint32_t)npix, q0, bg, p0.lo, tb, dstarts);
+            t, dcams, douts, (uint32_t)p0.nbf, bx, (uint32_t)npix, q0, bg, p0.lo, tb, dstarts, dsky);
         qrc = launch_queue_passes<false, BD, false, FUSE>(c, t, run);
     });
     if (!bd_ok) return fail(c, VHX_E_INVALID_ARG, "unsupported brick_dim");
