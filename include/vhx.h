@@ -18,6 +18,7 @@
  *                           BoxTree::get_by_ray (src/raytracing/cpu.rs:296-458) and the CPU frame of
  *                           examples/gpu_render.rs:196-257 / benches/performance.rs:29-66
  *   vhx_trace_rays       <- BoxTree::get_by_ray (src/raytracing/cpu.rs:296) over an explicit batch of rays
+ *   vhx_get_voxels       <- BoxTree::get (src/boxtree/mod.rs:223-317) over a batch of positions
  *   vhx_last_error       <- the Result<_, ()> / expect() error paths of the plugin (src/raytracing/bevy/streaming/mod.rs:63-73)
  *
  * Conventions: every function returns 0 on success or a negative VHX_E_* code; a message is kept per context
@@ -260,6 +261,35 @@ int vhx_tree_counts(const vhx_ctx *ctx, vhx_tree_desc *counts);
 int vhx_read_range(vhx_ctx *ctx, int buffer_id, uint64_t elem_offset, uint64_t elem_count, void *dst);
 /* Device bytes held by the uploaded tree. */
 int vhx_tree_device_bytes(const vhx_ctx *ctx, uint64_t *bytes);
+
+/* Reading voxels ---------------------------------------------------------------------------------------------- */
+/* BoxTree::get for n positions (3 u32 per position: x, y, z): values[i] is the PaletteIndexValues that
+ * get_internal(ROOT, root_bounds, position) returns (src/boxtree/mod.rs:247-317), VHX_EMPTY = none as in vhx_hits.value
+ * (the entry is pix_get_ref of it over the palettes). Case by case as the reference: a position outside the root cube is
+ * empty; the descent stops at the first node that is not Internal, or at an Internal node whose child entry is VHX_EMPTY
+ * (an empty sectant, or a child absent from a LOD-cut or streamed view), which reads as empty -- node MIPs are never
+ * consulted; a Leaf's Empty brick is empty, its Solid brick gives the brick's value as it is, its Parted brick the cell at
+ * matrix_index_for(child bounds), empty where that cell points to nothing in the palettes; a UniformLeaf gives its Solid
+ * brick's value, or the cell of its Parted brick at matrix_index_for(node bounds) as it is, WITHOUT the points-to-nothing
+ * test (so a value whose colour is transparent comes back raw there, as from the reference).
+ * on_device = 0: both pointers are host memory and the call returns when values is filled. 1: both are device memory and
+ * the work is queued on the context's stream; the two ranges must not overlap (VHX_E_INVALID_ARG). Ordered like a trace:
+ * allowed on shared contexts, and it sees every write of the tree submitted before it and none submitted after. n = 0
+ * succeeds and does nothing; at most 2^31 positions per call; VHX_E_STATE before any upload. */
+int vhx_get_voxels(vhx_ctx *ctx, const uint32_t *positions, uint64_t n, uint32_t *values, int on_device);
+/* A box of the tree as a dense albedo grid: the inverse of vhx_build_tree_dense. */
+typedef struct vhx_dense_out {
+    uint32_t ox, oy, oz;      /* min corner of the box in the tree */
+    uint32_t gx, gy, gz;      /* extents, >= 1; the box must lie inside the root cube: VHX_E_INVALID_ARG otherwise */
+    uint32_t *albedo;         /* voxel (ox+x, oy+y, oz+z) at albedo[((uint64_t)z*gy + y)*gx + x] */
+} vhx_dense_out;
+/* Writes, for every voxel of the box, the colour of v = vhx_get_voxels(position): color_palette[v & 0xFFFF] when v is not
+ * VHX_EMPTY, its colour index is neither 0xFFFF nor past the palette and that colour's alpha byte is not 0; else 0. So a
+ * voxel that carries only data reads as 0, and vhx_read_dense of vhx_build_tree_dense(g) (simplified or not) is g with
+ * its alpha-0 entries zeroed, zero-extended to the box. The walk is per aligned cube of voxels, not per voxel: whole
+ * empty regions and Solid bricks are constant fills, Parted bricks are copied through the palette. on_device, ordering
+ * and errors as vhx_get_voxels; a refused call leaves albedo untouched. */
+int vhx_read_dense(vhx_ctx *ctx, const vhx_dense_out *box, int on_device);
 
 /* Tracing --------------------------------------------------------------------------------------------------- */
 /* Traces primary rays for every pixel of the square tiles k = tile_start, tile_start+tile_stride, ... (raster order

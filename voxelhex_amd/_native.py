@@ -62,6 +62,11 @@ class DenseDesc(ctypes.Structure):  # vhx_dense_desc
                 ("reserved0", c_u32), ("albedo", c_void_p)]
 
 
+class DenseOut(ctypes.Structure):  # vhx_dense_out
+    _fields_ = [("ox", c_u32), ("oy", c_u32), ("oz", c_u32), ("gx", c_u32), ("gy", c_u32), ("gz", c_u32),
+                ("albedo", c_void_p)]
+
+
 class Range(ctypes.Structure):
     _fields_ = [("buffer_id", ctypes.c_int32), ("reserved0", c_u32), ("elem_offset", c_u64), ("elem_count", c_u64),
                 ("src", c_void_p)]
@@ -116,6 +121,8 @@ SIGNATURES = [
     ("vhx_build_tree_dense_simplified", c_int, [c_void_p, P(DenseDesc), c_int]),
     ("vhx_tree_counts", c_int, [c_void_p, P(TreeDesc)]),
     ("vhx_read_range", c_int, [c_void_p, c_int, c_u64, c_u64, c_void_p]),
+    ("vhx_get_voxels", c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_int]),
+    ("vhx_read_dense", c_int, [c_void_p, P(DenseOut), c_int]),
     ("vhx_set_node_mips", c_int, [c_void_p, c_void_p, c_u32]),
     ("vhx_update_range", c_int, [c_void_p, c_int, c_u64, c_u64, c_void_p]),
     ("vhx_update_ranges", c_int, [c_void_p, c_void_p, c_u32]),

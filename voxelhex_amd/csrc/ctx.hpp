@@ -1,5 +1,5 @@
 // Internal context of libvhx, shared by the translation units of the device side: vhx_device.hip (tracing), vhx_tree.hip
-// (the device tree), vhx_ctx.hip (contexts, ordering, settings), vhx_mgpu.hip and vhx_build.hip.
+// (the device tree), vhx_ctx.hip (contexts, ordering, settings), vhx_mgpu.hip, vhx_build.hip and vhx_query.hip.
 // Not part of the ABI: callers see vhx_ctx only as an opaque pointer (include/vhx.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -123,6 +123,7 @@ struct vhx_ctx {
     uint32_t shadow_next = 0;
     DevBuf shadow_args;
     DevBuf upd;
+    DevBuf query;  // vhx_get_voxels / vhx_read_dense with host pointers: the positions and values, or the grid, on the device
     hipStream_t upd_stream = nullptr;  // the stream of the last scatter (reads upd)
     // vhx_build_tree_dense (vhx_build.hip): scratch kept across builds and reset by each one -- the occupancy words of
     // every possible node per level (the leaves' are their brick masks), their breadth-first ranks and first brick

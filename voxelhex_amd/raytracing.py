@@ -4,6 +4,8 @@
     Raytracer                a libvhx context: one device, the tree resident in HBM (BoxTreeGPUHost + view,
                              src/raytracing/bevy/mod.rs:164-180, src/raytracing/bevy/view.rs:36-137)
     Raytracer.trace_rays     BoxTree::get_by_ray over a batch (src/raytracing/cpu.rs:296)
+    Raytracer.get            BoxTree::get over a batch of positions (src/boxtree/mod.rs:223-317); read_dense: a box of
+                             the tree as a dense albedo grid, the inverse of build_dense
     Raytracer.trace_primary  one frame of per-pixel primary rays (VhxRenderNode::run,
                              src/raytracing/bevy/pipeline/mod.rs:96-155, with the CPU frame semantics of
                              examples/gpu_render.rs:196-257)
@@ -293,6 +295,69 @@ class Raytracer:
                  d.data_count)
         arrays = {name: self.read_range(i, 0, n) for i, ((name, _), n) in enumerate(zip(TREE_ARRAYS, sizes))}
         return TreeImage(d.boxtree_size, d.brick_dim, arrays)
+
+    def _device_tensor(self, a, what):
+        """A contiguous int32 / uint32 tensor on this context's device, with torch's current stream synchronised (the
+        query runs on the context's stream, not on torch's)."""
+        import torch
+        if not a.is_cuda or a.device.index != self.device:
+            raise ValueError(f"{what}: the tensor must live on device {self.device}")
+        if a.dtype not in (torch.int32, torch.uint32) or not a.is_contiguous():
+            raise TypeError(f"{what}: a contiguous int32 / uint32 tensor")
+        torch.cuda.current_stream(a.device).synchronize()
+        return a
+
+    def get(self, positions):
+        """vhx_get_voxels: BoxTree::get for a batch of positions, as PaletteIndexValues (N.VHX_EMPTY = none;
+        boxtree.entry_from_value turns one into an entry over the palettes). `positions` is an (n, 3) integer numpy
+        array (x, y, z per row), which gives a numpy uint32 array, or a contiguous int32 / uint32 torch tensor of that
+        shape on this context's device, which gives a tensor of the same dtype there: torch's current stream is
+        synchronised before the call and the context before the tensor is handed back."""
+        if hasattr(positions, "data_ptr"):
+            import torch
+            if positions.dim() != 2 or positions.shape[1] != 3:
+                raise TypeError("get: positions of shape (n, 3)")
+            p = self._device_tensor(positions, "get")
+            out = torch.empty(p.shape[0], dtype=p.dtype, device=p.device)
+            self._check(N.lib().vhx_get_voxels(self._h, p.data_ptr(), p.shape[0], out.data_ptr(), 1))
+            self.sync()
+            return out
+        p = np.asarray(positions)
+        if p.ndim != 2 or p.shape[1] != 3 or p.dtype.kind not in "iu":
+            raise TypeError("get: an integer array of shape (n, 3)")
+        if p.size and (int(p.min()) < 0 or int(p.max()) > 0xFFFFFFFF):
+            raise ValueError("get: positions are unsigned 32-bit")
+        p = np.ascontiguousarray(p.astype(np.uint32, copy=False))
+        out = np.empty(p.shape[0], np.uint32)
+        self._check(N.lib().vhx_get_voxels(self._h, p.ctypes.data, p.shape[0], out.ctypes.data, 0))
+        return out
+
+    def read_dense(self, origin=(0, 0, 0), extents=None, out=None):
+        """vhx_read_dense: the box at `origin` (x, y, z) with `extents` (gx, gy, gz; None = the whole root cube) as a
+        dense grid of shape (gz, gy, gx) of packed albedos, 0 where there is no visible voxel -- the inverse of
+        build_dense. `out` (optional) receives it: a C-contiguous uint32 numpy array, or a contiguous int32 / uint32
+        torch tensor on this context's device (synchronised like get's); without it a numpy array is returned."""
+        ox, oy, oz = (int(v) for v in origin)
+        if extents is None:
+            extents = (self.tree_counts().boxtree_size,) * 3
+        gx, gy, gz = (int(v) for v in extents)
+        if min(ox, oy, oz) < 0 or min(gx, gy, gz) < 0:
+            raise ValueError("read_dense: origin and extents are unsigned")
+        if out is None:
+            out = np.empty((gz, gy, gx), np.uint32)
+        if tuple(out.shape) != (gz, gy, gx):
+            raise ValueError(f"read_dense: out has shape {tuple(out.shape)}, the box needs {(gz, gy, gx)}")
+        box = N.DenseOut(ox, oy, oz, gx, gy, gz, None)
+        if hasattr(out, "data_ptr"):
+            box.albedo = self._device_tensor(out, "read_dense").data_ptr()
+            self._check(N.lib().vhx_read_dense(self._h, ctypes.byref(box), 1))
+            self.sync()
+            return out
+        if out.dtype != np.uint32 or not out.flags.c_contiguous:
+            raise TypeError("read_dense: out is a C-contiguous uint32 array")
+        box.albedo = out.ctypes.data
+        self._check(N.lib().vhx_read_dense(self._h, ctypes.byref(box), 0))
+        return out
 
     def update_range(self, buffer_id, elem_offset, values):
         values = np.ascontiguousarray(values)
