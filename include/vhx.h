@@ -290,6 +290,33 @@ typedef struct vhx_dense_out {
  * empty regions and Solid bricks are constant fills, Parted bricks are copied through the palette. on_device, ordering
  * and errors as vhx_get_voxels; a refused call leaves albedo untouched. */
 int vhx_read_dense(vhx_ctx *ctx, const vhx_dense_out *box, int on_device);
+/* A box of the tree replaced by a dense albedo grid, on the device and in place: the inverse of vhx_read_dense, and the
+ * counterpart of BoxTree::insert / clear for a tree without a host tree behind it. */
+#define VHX_WRITE_REPLACE 0u  /* every voxel of the box becomes the grid's; alpha byte 0 = no voxel (clears) */
+#define VHX_WRITE_INSERT  1u  /* grid voxels with alpha byte 0 leave the tree's voxel as it is */
+typedef struct vhx_dense_in {
+    uint32_t ox, oy, oz;      /* min corner of the box in the tree */
+    uint32_t gx, gy, gz;      /* extents >= 1; the box must lie inside the root cube: VHX_E_INVALID_ARG otherwise */
+    uint32_t mode;            /* VHX_WRITE_* */
+    uint32_t fill;            /* used when albedo == NULL: every voxel of the box is this colour (0 clears) */
+    const uint32_t *albedo;   /* voxel (ox+x, oy+y, oz+z) at albedo[((uint64_t)z*gy + y)*gx + x]; may be NULL */
+} vhx_dense_in;
+/* After the call vhx_read_dense of the root cube is what it was with the box replaced, vhx_get_voxels of a written voxel
+ * is its palette index | 0xFFFF0000 (VHX_EMPTY where cleared; data values of overwritten voxels are dropped) and every
+ * other voxel reads as before. Touched leaves become Leaf nodes (a UniformLeaf is expanded in place), bricks the box
+ * meets become Parted bricks (rewritten in their slot, or given a new one), emptied bricks and nodes are unlinked up to
+ * the root; new nodes, bricks and colours are appended after node_count, brick_count and color_count, a colour the
+ * palette holds keeps its lowest index; solid_values and data_palette never change. Slots are not reused and nothing is
+ * re-simplified (vhx_tree_orphans counts the unlinked slots; vhx_read_dense + vhx_build_tree_dense compacts). The tree's
+ * buffers grow as needed, contents kept, and vhx_tree_counts reports the new counts. on_device as
+ * vhx_build_tree_dense. Ordered like vhx_update_ranges: owner context only (VHX_E_STATE on a shared one), frames
+ * submitted before it see the old tree, frames after it the new one; returns when the tree is ready. A refused call
+ * leaves the tree as it was: VHX_E_STATE before any upload, while node MIPs are set, or when the tree under the box is
+ * not of canonical depth (a LOD-cut or streamed view); VHX_E_CAPACITY past 65,535 colours, 2^31 bricks or 2^28 touched
+ * leaf cubes; VHX_E_INVALID_ARG for a bad box or mode. */
+int vhx_write_dense(vhx_ctx *ctx, const vhx_dense_in *box, int on_device);
+/* Node and brick slots that vhx_write_dense has unlinked since the last upload or build. */
+int vhx_tree_orphans(const vhx_ctx *ctx, uint32_t *nodes, uint32_t *bricks);
 
 /* Tracing --------------------------------------------------------------------------------------------------- */
 /* Traces primary rays for every pixel of the square tiles k = tile_start, tile_start+tile_stride, ... (raster order

@@ -26,8 +26,9 @@ HOST_SRCS = ["boxtree.cpp", "flatten.cpp", "vox.cpp", "stream.cpp"]
 # arithmetic and its rounding are unchanged). Bench frame at eight frames in flight 0.592-0.602 ms against 0.613-0.616
 # with the default scheduler; trace kernels 70 / 97 VGPRs against 75 / 102 (profiles/r02/sched_variants_f8.log)
 DEV_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
-DEV_SRCS = ["vhx_device.hip", "vhx_tree.hip", "vhx_ctx.hip", "vhx_mgpu.hip", "vhx_build.hip", "vhx_query.hip"]
-HEADERS = ["boxtree.hpp", "trace.hpp", "ctx.hpp", "skyblock.hpp"]
+DEV_SRCS = ["vhx_device.hip", "vhx_tree.hip", "vhx_ctx.hip", "vhx_mgpu.hip", "vhx_build.hip", "vhx_query.hip",
+            "vhx_edit.hip"]
+HEADERS = ["boxtree.hpp", "trace.hpp", "ctx.hpp", "skyblock.hpp", "buildtab.hpp", "treewalk.hpp"]
 
 
 def _hipcc():

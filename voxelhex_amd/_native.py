@@ -46,6 +46,7 @@ VHX_SCENE_CUBE, VHX_SCENE_BOUNDARY, VHX_SCENE_HEIGHTFIELD = 4, 5, 6
 VHX_BUF_NODE_TYPE, VHX_BUF_NODE_OCBITS, VHX_BUF_NODE_CHILDREN, VHX_BUF_VOXELS = 0, 1, 2, 3
 VHX_BUF_SOLID_VALUES, VHX_BUF_COLOR_PALETTE, VHX_BUF_DATA_PALETTE = 4, 5, 6
 VHX_DERIVED_NODE_HDR, VHX_DERIVED_BRICK_OCC = 0, 1
+VHX_WRITE_REPLACE, VHX_WRITE_INSERT = 0, 1
 
 
 class TreeDesc(ctypes.Structure):
@@ -65,6 +66,11 @@ class DenseDesc(ctypes.Structure):  # vhx_dense_desc
 class DenseOut(ctypes.Structure):  # vhx_dense_out
     _fields_ = [("ox", c_u32), ("oy", c_u32), ("oz", c_u32), ("gx", c_u32), ("gy", c_u32), ("gz", c_u32),
                 ("albedo", c_void_p)]
+
+
+class DenseIn(ctypes.Structure):  # vhx_dense_in
+    _fields_ = [("ox", c_u32), ("oy", c_u32), ("oz", c_u32), ("gx", c_u32), ("gy", c_u32), ("gz", c_u32),
+                ("mode", c_u32), ("fill", c_u32), ("albedo", c_void_p)]
 
 
 class Range(ctypes.Structure):
@@ -123,6 +129,8 @@ SIGNATURES = [
     ("vhx_read_range", c_int, [c_void_p, c_int, c_u64, c_u64, c_void_p]),
     ("vhx_get_voxels", c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_int]),
     ("vhx_read_dense", c_int, [c_void_p, P(DenseOut), c_int]),
+    ("vhx_write_dense", c_int, [c_void_p, P(DenseIn), c_int]),
+    ("vhx_tree_orphans", c_int, [c_void_p, P(c_u32), P(c_u32)]),
     ("vhx_set_node_mips", c_int, [c_void_p, c_void_p, c_u32]),
     ("vhx_update_range", c_int, [c_void_p, c_int, c_u64, c_u64, c_void_p]),
     ("vhx_update_ranges", c_int, [c_void_p, c_void_p, c_u32]),

@@ -1,5 +1,6 @@
 // Internal context of libvhx, shared by the translation units of the device side: vhx_device.hip (tracing), vhx_tree.hip
-// (the device tree), vhx_ctx.hip (contexts, ordering, settings), vhx_mgpu.hip, vhx_build.hip and vhx_query.hip.
+// (the device tree), vhx_ctx.hip (contexts, ordering, settings), vhx_mgpu.hip, vhx_build.hip, vhx_query.hip and
+// vhx_edit.hip.
 // Not part of the ABI: callers see vhx_ctx only as an opaque pointer (include/vhx.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,6 +34,8 @@ struct TreeStore {
     // iteration whose target child is occupied but absent probes the node's MIP (vhx_set_node_mips)
     DevBuf mips;
     bool mips_on = false;
+    // node and brick slots that vhx_write_dense left unreferenced since the last upload or build (vhx_tree_orphans)
+    uint32_t orphan_nodes = 0, orphan_bricks = 0;
     // Ordering of tree writes against frames in flight (any context of the tree, any stream; no host waits): a write
     // (upload, ranged update, node MIPs) first makes its stream wait for the last submitted trace of every other
     // context (their use_ev), and records write_ev after it; a context's next trace waits for write_ev once per write
@@ -133,6 +136,13 @@ struct vhx_ctx {
     struct BuildScratch {
         DevBuf occ, rank, first, part, table, ctl, grid, simp;
     } build;
+    // vhx_write_dense (vhx_edit.hip): per level of the box's lattice of aligned cubes the old node of every cube, its
+    // occupancy after the write, the "needs a new node" words with their ranks, the leaves' new-brick masks and first
+    // new bricks, and the counters read back. Reset by each call; the colour table, the scans' block sums and the
+    // device copy of a host grid are the build's
+    struct EditScratch {
+        DevBuf oldn, aft, need, rank, nmask, first, ctl;
+    } edit;
     // depth-prepass mode (vhx_set_depth_prepass; opt-in, not the reference path)
     bool prepass = false, in_prepass = false;
     // fused hard shadows (vhx_set_shadow_light): each hit's shadow ray traced in the lane that finished its primary ray
@@ -296,6 +306,10 @@ uint64_t elem_size(int id);
 uint64_t elem_count(const vhx_tree_desc &d, int id);
 // allocates the raw buffers for the counts of *t (t's pointers unused) and records the counts
 int alloc_tree(vhx_ctx *c, const vhx_tree_desc *t);
+// vhx_write_dense: room for the counts of *t in the raw and derived buffers, contents kept. A buffer that is too small
+// is replaced by a larger one (by half again at least) filled by a device copy on c's stream; the old ones are freed
+// after a wait for that stream, which (inside a WriteScope) already waits for the frames in flight
+int grow_tree(vhx_ctx *c, const vhx_tree_desc *t);
 // derives the device-side layout (node headers, brick bitmaps, child records) from the raw buffers, synchronously
 int finish_upload(vhx_ctx *c);
 // rebuilds DevTree::child_rec on c's stream when an update left it stale (every trace calls it before its first launch)

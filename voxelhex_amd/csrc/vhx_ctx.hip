@@ -231,7 +231,8 @@ void vhx_destroy(vhx_ctx *c) {
                       &c->flags, &c->qargs, &c->state, &c->stateq, &c->upd, &c->prepass_depth, &c->batch_args, &c->scan_part,
                       &c->shadow_args, &c->tail_list[0], &c->tail_list[1], &c->tail_mask, &c->build.occ, &c->build.rank,
                       &c->build.first, &c->build.part, &c->build.table, &c->build.ctl, &c->build.grid,
-                      &c->build.simp, &c->sky, &c->query})
+                      &c->build.simp, &c->sky, &c->query, &c->edit.oldn, &c->edit.aft, &c->edit.need,
+                      &c->edit.rank, &c->edit.nmask, &c->edit.first, &c->edit.ctl})
         if (b->ptr) (void)hipFree(b->ptr);
     if (c->tail_stream) {
         (void)hipStreamSynchronize(c->tail_stream);

@@ -4,7 +4,7 @@
 //   k_get_voxels     BoxTree::get (src/boxtree/mod.rs:223-317) for a batch of positions, one lane per position
 //   k_read_dense     a box of the tree as a dense albedo grid, tree driven: one workgroup per aligned cube of voxels
 // Host side: vhx_get_voxels, vhx_read_dense. Both are ordered like a trace (TraceScope) and launch no kernel of another
-// unit except through refresh_child_rec.
+// unit except through refresh_child_rec. Wave-uniform loads and the sectant of a position come from treewalk.hpp.
 //
 // The walk runs in integers (DESIGN.md §8.6 argues why that equals the reference's f32 sectant_for / matrix_index_for):
 // boxtree_size = brick_dim * 4^k with brick_dim a power of two, so a node's cube is 2^lg voxels wide and aligned to its
@@ -18,6 +18,7 @@
 #include "../../include/vhx.h"
 #include "ctx.hpp"
 #include "trace.hpp"
+#include "treewalk.hpp"
 
 using namespace vhx;
 
@@ -30,17 +31,6 @@ struct QShape {
     uint32_t levels;   // node levels: the root is level 0, the smallest leaf (4 * brick_dim wide) level levels - 1
     uint32_t brick_count, solid_count;
 };
-
-// A load the whole wave makes at one address: through the constant address space, so that it is a scalar load where the
-// compiler can prove the address uniform. The tree is only ever written by earlier launches.
-__device__ __forceinline__ uint32_t uload(const uint32_t *p) {
-    return *(const __attribute__((address_space(4))) uint32_t *)(uintptr_t)p;
-}
-
-__device__ __forceinline__ uint32_t sectant_of(uint32_t x, uint32_t y, uint32_t z, uint32_t lg) {
-    const uint32_t sh = lg - 2u;
-    return ((x >> sh) & 3u) | (((y >> sh) & 3u) << 2) | (((z >> sh) & 3u) << 4);
-}
 
 // the colour vhx_read_dense writes for a value: the palette entry of its colour index unless that is none, out of the
 // palette or transparent (VHX_EMPTY has colour index 0xFFFF)

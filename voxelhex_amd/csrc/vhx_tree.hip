@@ -6,7 +6,7 @@
 //   k_child_rec       DevTree::child_rec (brick_dim <= 4): one record per child entry
 //   k_scatter_ranges  ranged writes: staged pieces copied to their device addresses
 // Host side: upload (vhx_upload_tree*, receive_tree), ranged updates (vhx_update_range(s)), node MIPs, read-back of the
-// derived layout. Launches no kernel of another unit; the trace unit (vhx_device.hip) calls refresh_child_rec.
+// derived layout, content-preserving growth of the buffers for vhx_write_dense (grow_tree), vhx_tree_orphans. Launches no kernel of another unit; the trace unit (vhx_device.hip) calls refresh_child_rec.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,18 +17,11 @@
 
 #include "../../include/vhx.h"
 #include "ctx.hpp"
+#include "treewalk.hpp"
 
 using namespace vhx;
 
 // ------------------------------------------------------------------------------------------------ upload kernels
-__device__ __forceinline__ bool cell_empty(uint32_t v, const uint32_t *color, uint32_t ncolor, const uint32_t *data,
-                                           uint32_t ndata) {
-    const uint32_t ci = v & 0xFFFFu, di = v >> 16;
-    const bool cn = ci == 0xFFFFu || ci >= ncolor || ((color[ci] >> 24) & 0xFFu) == 0;
-    const bool dn = di == 0xFFFFu || di >= ndata || data[di] == 0;
-    return cn && dn;
-}
-
 // bd^3 >= 64: one lane per cell, the wave's ballot is one 64-bit occupancy word
 __global__ void __launch_bounds__(256) k_brick_occ_ballot(const uint32_t *__restrict__ vox, uint64_t ncells,
                                                           uint64_t cell0, const uint32_t *__restrict__ color,
@@ -225,6 +218,7 @@ int vhx::alloc_tree(vhx_ctx *c, const vhx_tree_desc *t) {
     if (grows && c->stream) VHX_HIP(c, hipStreamSynchronize(c->stream));
     c->tree->uploaded = false;
     c->tree->mips_on = false;  // a new tree has no MIPs until vhx_set_node_mips
+    c->tree->orphan_nodes = c->tree->orphan_bricks = 0;
     for (int id = 0; id < 7; ++id) {
         int rc = ensure(c, c->tree->raw[id], elem_count(*t, id) * elem_size(id));
         if (rc) return rc;
@@ -235,6 +229,40 @@ int vhx::alloc_tree(vhx_ctx *c, const vhx_tree_desc *t) {
                            (const void **)&c->tree->desc.solid_values, (const void **)&c->tree->desc.color_palette,
                            (const void **)&c->tree->desc.data_palette})
         *q = nullptr;  // only the counts are kept
+    return VHX_OK;
+}
+
+int vhx::grow_tree(vhx_ctx *c, const vhx_tree_desc *t) {
+    TreeStore &ts = *c->tree;
+    const vhx_tree_desc &d = ts.desc;
+    struct Want {
+        DevBuf *b;
+        uint64_t used, need;
+    } want[10];
+    uint32_t n = 0;
+    for (int id = 0; id < 7; ++id)
+        want[n++] = {&ts.raw[id], elem_count(d, id) * elem_size(id), elem_count(*t, id) * elem_size(id)};
+    want[n++] = {&ts.hdr, (uint64_t)d.node_count * 16, (uint64_t)t->node_count * 16};
+    want[n++] = {&ts.brick_occ, (uint64_t)d.brick_count * ts.occ_words * 8, (uint64_t)t->brick_count * ts.occ_words * 8};
+    if (has_child_rec(c)) want[n++] = {&ts.child_rec, (uint64_t)d.node_count * 1024, (uint64_t)t->node_count * 1024};
+    void *old[10];
+    uint32_t nold = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        DevBuf &b = *want[i].b;
+        if (b.ptr && b.bytes >= want[i].need) continue;
+        const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(want[i].need, b.bytes + b.bytes / 2), 16);
+        void *p = nullptr;
+        VHX_HIP(c, hipMalloc(&p, cap));
+        if (b.ptr && want[i].used)
+            VHX_HIP(c, hipMemcpyAsync(p, b.ptr, std::min(want[i].used, b.bytes), hipMemcpyDeviceToDevice, c->stream));
+        if (b.ptr) old[nold++] = b.ptr;
+        b.ptr = p;
+        b.bytes = cap;
+    }
+    if (nold) {
+        VHX_HIP(c, hipStreamSynchronize(c->stream));
+        for (uint32_t i = 0; i < nold; ++i) VHX_HIP(c, hipFree(old[i]));
+    }
     return VHX_OK;
 }
 
@@ -484,6 +512,14 @@ int vhx_tree_device_bytes(const vhx_ctx *c, uint64_t *bytes) {
     uint64_t b = c->tree->hdr.bytes + c->tree->brick_occ.bytes + c->tree->child_rec.bytes;
     for (auto &r : c->tree->raw) b += r.bytes;
     *bytes = b;
+    return VHX_OK;
+}
+
+int vhx_tree_orphans(const vhx_ctx *c, uint32_t *nodes, uint32_t *bricks) {
+    if (!c || !nodes || !bricks) return VHX_E_INVALID_ARG;
+    if (!c->tree->uploaded) return VHX_E_STATE;
+    *nodes = c->tree->orphan_nodes;
+    *bricks = c->tree->orphan_bricks;
     return VHX_OK;
 }
 

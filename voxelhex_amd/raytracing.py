@@ -359,6 +359,46 @@ class Raytracer:
         self._check(N.lib().vhx_read_dense(self._h, ctypes.byref(box), 0))
         return out
 
+    def write_dense(self, grid, origin=(0, 0, 0), mode="replace"):
+        """vhx_write_dense: the box at `origin` (x, y, z) with the extents of `grid` (shape (gz, gy, gx), packed albedos as
+        for build_dense) replaced on the device, in place -- the inverse of read_dense. mode "replace": every voxel of
+        the box becomes the grid's, alpha 0 clears; "insert": grid voxels with alpha 0 leave the tree as it is. `grid` is
+        a uint32 numpy array (copied to the device first) or a contiguous int32 / uint32 torch tensor on this context's
+        device, read in place (torch's current stream is synchronised before the call). Owner context only; the call
+        returns when the tree is ready."""
+        modes = {"replace": N.VHX_WRITE_REPLACE, "insert": N.VHX_WRITE_INSERT}
+        box = N.DenseIn()
+        box.ox, box.oy, box.oz = (int(v) for v in origin)
+        box.mode = modes[mode] if mode in modes else int(mode)
+        if hasattr(grid, "data_ptr"):
+            if grid.dim() != 3:
+                raise TypeError("write_dense: a tensor of shape (gz, gy, gx)")
+            grid = self._device_tensor(grid, "write_dense")
+            box.albedo, on_device = grid.data_ptr(), 1
+        else:
+            grid = np.ascontiguousarray(grid, np.uint32)
+            if grid.ndim != 3:
+                raise TypeError("write_dense: an array of shape (gz, gy, gx)")
+            box.albedo, on_device = grid.ctypes.data, 0
+        box.gz, box.gy, box.gx = (int(v) for v in grid.shape)
+        self._check(N.lib().vhx_write_dense(self._h, ctypes.byref(box), on_device))
+
+    def fill_box(self, origin, extents, albedo):
+        """vhx_write_dense without a grid: every voxel of the box at `origin` with `extents` (gx, gy, gz) becomes the
+        packed colour `albedo`; 0 (or any colour with alpha 0) clears the box."""
+        box = N.DenseIn()
+        box.ox, box.oy, box.oz = (int(v) for v in origin)
+        box.gx, box.gy, box.gz = (int(v) for v in extents)
+        box.mode, box.fill, box.albedo = N.VHX_WRITE_REPLACE, int(albedo), None
+        self._check(N.lib().vhx_write_dense(self._h, ctypes.byref(box), 0))
+
+    def orphans(self):
+        """vhx_tree_orphans: (nodes, bricks) that write_dense / fill_box unlinked since the last upload or build; their
+        slots are not reused (read_dense + build_dense compacts)."""
+        n, b = ctypes.c_uint32(), ctypes.c_uint32()
+        self._check(N.lib().vhx_tree_orphans(self._h, ctypes.byref(n), ctypes.byref(b)))
+        return n.value, b.value
+
     def update_range(self, buffer_id, elem_offset, values):
         values = np.ascontiguousarray(values)
         self._check(N.lib().vhx_update_range(self._h, buffer_id, elem_offset, values.size, values.ctypes.data))
