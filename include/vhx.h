@@ -307,7 +307,7 @@ typedef struct vhx_dense_in {
  * meets become Parted bricks (rewritten in their slot, or given a new one), emptied bricks and nodes are unlinked up to
  * the root; new nodes, bricks and colours are appended after node_count, brick_count and color_count, a colour the
  * palette holds keeps its lowest index; solid_values and data_palette never change. Slots are not reused and nothing is
- * re-simplified (vhx_tree_orphans counts the unlinked slots; vhx_read_dense + vhx_build_tree_dense compacts). The tree's
+ * re-simplified (vhx_tree_orphans counts the unlinked slots; vhx_compact_tree drops them). The tree's
  * buffers grow as needed, contents kept, and vhx_tree_counts reports the new counts. on_device as
  * vhx_build_tree_dense. Ordered like vhx_update_ranges: owner context only (VHX_E_STATE on a shared one), frames
  * submitted before it see the old tree, frames after it the new one; returns when the tree is ready. A refused call
@@ -317,6 +317,25 @@ typedef struct vhx_dense_in {
 int vhx_write_dense(vhx_ctx *ctx, const vhx_dense_in *box, int on_device);
 /* Node and brick slots that vhx_write_dense has unlinked since the last upload or build. */
 int vhx_tree_orphans(const vhx_ctx *ctx, uint32_t *nodes, uint32_t *bricks);
+/* Rewrites the resident tree on the device without its unreachable slots and in the builders' numbering: the image of
+ * vhx_flat_compact (vhx_boxtree.h) of the tree, bit for bit. Nodes are renumbered breadth-first from the root, Parted
+ * bricks in (owning node, sectant) order; node types, occupancy, cells, solid_values and both palettes (with their
+ * counts) stay as they are, so every vhx_get_voxels, vhx_read_dense and trace result is unchanged. node_count and
+ * brick_count become the reachable counts (vhx_tree_counts), vhx_tree_orphans reports (0, 0), and the buffers shrink
+ * to what an upload of the new image would hold (vhx_tree_device_bytes). *nodes_dropped / *bricks_dropped (either may
+ * be NULL) receive the slots that left. A freshly built or uploaded canonical tree comes back as it is.
+ * The call works out of place: new raw and derived buffers are allocated at the new counts, filled and swapped in, and
+ * the old ones are freed once the frames in flight have finished with them, so the peak device memory is the old tree
+ * plus the new one. Nothing of the old tree is written: a refused call or a failed allocation leaves it as it was.
+ * Ordered like vhx_write_dense: owner context only (VHX_E_STATE on a shared one), frames submitted before it trace the
+ * old buffers, frames after it, on any context, the new ones; returns when the tree is ready. VHX_E_STATE before any
+ * upload, while node MIPs are set (their descriptors name brick slots that move), and for a malformed tree (a child
+ * index at or past node_count, a Parted index at or past brick_count, a node or Parted brick reached twice, more than
+ * 8 node levels). A vhx_sync after the call reports the device time of its gather pass (voxels and bitmaps) in place
+ * of a trace's.
+ * Node MIP descriptors computed before a compaction are invalid after it. A streamed view's host cache (vhx_stream.h)
+ * keeps slot numbers of the device buffers: compacting under it invalidates them, so the caller must not do it. */
+int vhx_compact_tree(vhx_ctx *ctx, uint32_t *nodes_dropped, uint32_t *bricks_dropped);
 
 /* Tracing --------------------------------------------------------------------------------------------------- */
 /* Traces primary rays for every pixel of the square tiles k = tile_start, tile_start+tile_stride, ... (raster order

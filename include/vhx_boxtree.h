@@ -26,6 +26,7 @@
  *                                 scene voxel by voxel (x, then y, then z loops) would produce
  *   vhx_dense_build            <- the same for a caller's dense voxel grid (vhx_dense_desc, vhx.h)
  *   vhx_dense_build_simplified <- that tree after BoxTree::simplify(ROOT, recursive), as load_vox_file leaves a model
+ *   vhx_flat_compact           <- no reference counterpart: an edited image without its orphaned slots, renumbered
  *
  * Tree type parameter: T = u32 (the reference default, BoxTree<T = u32>, src/boxtree/types.rs:219).
  */
@@ -153,6 +154,17 @@ int vhx_dense_build_simplified(const vhx_dense_desc *grid, int threads, vhx_flat
 int vhx_flat_node_mips(const vhx_flat *flat, const uint32_t **node_mips, uint32_t *count);
 /* Fills *desc with pointers into the flat object (valid until vhx_flat_free). */
 int vhx_flat_desc(const vhx_flat *flat, vhx_tree_desc *desc);
+/* The image `tree` (host arrays, e.g. a downloaded device tree after vhx_write_dense) without its unreachable slots and
+ * in the builders' numbering: the CPU counterpart of vhx_compact_tree (vhx.h), bit for bit. A node or Parted brick is
+ * reachable when a walk from node 0 finds it through the entries (an Internal node's entries that are not VHX_EMPTY, a
+ * Leaf's 64, a UniformLeaf's entry 0; occupied_bits are not consulted, so a LOD-cut view compacts like any tree). Nodes
+ * are renumbered breadth-first, level by level in (parent's new index, sectant) order, bricks in (owning node's new
+ * index, sectant) order; types, occupancy, cells, solid values and palettes move unchanged, and only child indices and
+ * Parted brick indices are rewritten. A freshly built image is returned as it is. Node MIPs are not carried over.
+ * VHX_E_INVALID_ARG for null arrays or a count of 0 nodes; VHX_E_TREE_INVALID_STRUCTURE, and no image, for a child
+ * index at or past node_count, a Parted index at or past brick_count, a node or Parted brick reached twice, or more
+ * than 8 node levels. */
+int vhx_flat_compact(const vhx_tree_desc *tree, vhx_flat **out);
 void vhx_flat_free(vhx_flat *flat);
 
 /* MagicaVoxel .vox import — BoxTree::<u32>::load_vox_file(filename, brick_dimension) (src/convert/magicavoxel.rs:

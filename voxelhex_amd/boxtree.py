@@ -274,9 +274,23 @@ def _dense_desc(grid, size, brick_dim):
     return d, g
 
 
+def _compacted(image):
+    """vhx_flat_compact of a FlatTree or TreeImage, as a new FlatTree."""
+    h = ctypes.c_void_p()
+    _tree_check(N.lib().vhx_flat_compact(ctypes.byref(image.desc), ctypes.byref(h)), "compacted: a malformed image")
+    return FlatTree(h.value)
+
+
 class TreeImage:
     """A flattened tree held in numpy arrays (Raytracer.download): the seven arrays and counts of a vhx_tree_desc,
     under FlatTree's names; `desc` points into them, so the image uploads, traces on the oracle and saves like one."""
+
+    def compacted(self):
+        """vhx_flat_compact: this image without its unreachable node and brick slots, renumbered as the builders number
+        (nodes breadth-first, bricks in (node, sectant) order), as a FlatTree -- what Raytracer.compact leaves on the
+        device, bit for bit. Cells, solid values and palettes are unchanged. InvalidStructure for a malformed image (an
+        index past its count, a node or brick reached twice, more than 8 levels)."""
+        return _compacted(self)
 
     def __init__(self, boxtree_size, brick_dim, arrays):
         self.desc = N.TreeDesc()
@@ -346,6 +360,10 @@ class FlatTree:
     def nbytes(self):
         return sum(a.nbytes for a in (self.node_type, self.node_ocbits, self.node_children, self.voxels,
                                       self.solid_values, self.color_palette, self.data_palette))
+
+    def compacted(self):
+        """vhx_flat_compact (see TreeImage.compacted): a freshly built image comes back equal to itself."""
+        return _compacted(self)
 
     @classmethod
     def _from_handle(cls, h):

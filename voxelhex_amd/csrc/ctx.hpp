@@ -1,6 +1,6 @@
 // Internal context of libvhx, shared by the translation units of the device side: vhx_device.hip (tracing), vhx_tree.hip
-// (the device tree), vhx_ctx.hip (contexts, ordering, settings), vhx_mgpu.hip, vhx_build.hip, vhx_query.hip and
-// vhx_edit.hip.
+// (the device tree), vhx_ctx.hip (contexts, ordering, settings), vhx_mgpu.hip, vhx_build.hip, vhx_query.hip,
+// vhx_edit.hip and vhx_compact.hip.
 // Not part of the ABI: callers see vhx_ctx only as an opaque pointer (include/vhx.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -143,6 +143,13 @@ struct vhx_ctx {
     struct EditScratch {
         DevBuf oldn, aft, need, rank, nmask, first, ctl;
     } edit;
+    // vhx_compact_tree (vhx_compact.hip): new index of every old node and the inverse, per new node the mask of its
+    // child entries with the rank of its first child and the mask of its Parted entries with its first new brick, the
+    // new index of every old brick (the claims) and the inverse, and the counters read back. Reset by each call; the
+    // scans' block sums are the build's
+    struct CompactScratch {
+        DevBuf new_of, old_of, nmask, nrank, bmask, bfirst, bnew, bsrc, ctl;
+    } compact;
     // depth-prepass mode (vhx_set_depth_prepass; opt-in, not the reference path)
     bool prepass = false, in_prepass = false;
     // fused hard shadows (vhx_set_shadow_light): each hit's shadow ray traced in the lane that finished its primary ray
@@ -312,6 +319,21 @@ int alloc_tree(vhx_ctx *c, const vhx_tree_desc *t);
 int grow_tree(vhx_ctx *c, const vhx_tree_desc *t);
 // derives the device-side layout (node headers, brick bitmaps, child records) from the raw buffers, synchronously
 int finish_upload(vhx_ctx *c);
+// vhx_compact_tree: the buffers of a compacted tree, allocated at the counts of `counts` and filled on c's stream
+// (palettes: a null ptr keeps the tree's own buffer)
+struct FreshTree {
+    DevBuf raw[7], hdr, brick_occ, child_rec;
+};
+// bytes an upload of `counts` gives buffer VHX_BUF_* `id` (ensure's rule: a buffer of no elements still has 16 bytes)
+uint64_t raw_bytes(const vhx_tree_desc &counts, int id);
+// allocates fresh->hdr, brick_occ, child_rec (brick_dim <= 4) and the four node and voxel buffers at `counts`, and a
+// palette buffer where the tree's own is larger than an upload's; on failure frees what it allocated: the tree is untouched
+int alloc_fresh_tree(vhx_ctx *c, const vhx_tree_desc &counts, FreshTree *fresh);
+void free_fresh_tree(FreshTree *fresh);
+// makes `fresh` (raw buffers and bitmaps filled) the tree of c's store with the counts of `counts`: copies the kept
+// palettes, swaps the buffers in, derives headers and child records from them with finish_upload's kernels, waits for
+// c's stream (which inside a WriteScope already waits for the frames in flight) and frees the old buffers
+int adopt_fresh_tree(vhx_ctx *c, const vhx_tree_desc &counts, FreshTree *fresh);
 // rebuilds DevTree::child_rec on c's stream when an update left it stale (every trace calls it before its first launch)
 int refresh_child_rec(vhx_ctx *c);
 // k_untile_planes on `stream` (arguments as vhx_untile_frame, already validated)

@@ -552,6 +552,84 @@ static int build_dense(const vhx_dense_desc *g, int threads, vhx_flat **out) {
     return VHX_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- compaction
+// The image without its unreachable slots, in the builders' numbering: nodes breadth-first from the
+// root, level by level in (parent's new index, sectant) order; Parted bricks in (owning node's new index, sectant)
+// order. Reachability goes by the entries, never by occupied_bits. The CPU reference of vhx_compact_tree.
+static constexpr uint32_t COMPACT_MAX_LEVELS = 8;  // node levels, as the device builders' MAX_LEVELS
+
+static int compact_image(const vhx_tree_desc &t, vhx_flat **out) {
+    const uint32_t nn = t.node_count, nb = t.brick_count;
+    const uint64_t n3 = (uint64_t)t.brick_dim * t.brick_dim * t.brick_dim;
+    if (nn == 0 || n3 == 0 || !t.node_type || !t.node_ocbits || !t.node_children || (nb && !t.voxels) ||
+        (t.solid_count && !t.solid_values) || (t.color_count && !t.color_palette) || (t.data_count && !t.data_palette))
+        return VHX_E_INVALID_ARG;
+    std::vector<uint32_t> new_of(nn, VHX_EMPTY), old_of{0};
+    new_of[0] = 0;
+    uint32_t levels = 0;
+    for (size_t begin = 0; begin < old_of.size();) {
+        if (++levels > COMPACT_MAX_LEVELS) return VHX_E_TREE_INVALID_STRUCTURE;
+        const size_t end = old_of.size();
+        for (size_t i = begin; i < end; ++i) {
+            const uint32_t o = old_of[i];
+            if (t.node_type[o] != VHX_NODE_INTERNAL) continue;
+            for (uint32_t s = 0; s < 64; ++s) {
+                const uint32_t e = t.node_children[(size_t)o * 64 + s];
+                if (e == VHX_EMPTY) continue;
+                if (e >= nn || new_of[e] != VHX_EMPTY) return VHX_E_TREE_INVALID_STRUCTURE;  // past the count, or twice
+                new_of[e] = (uint32_t)old_of.size();
+                old_of.push_back(e);
+            }
+        }
+        begin = end;
+    }
+    auto parted = [](uint32_t e) { return e != VHX_EMPTY && (e & VHX_SOLID_BIT) == 0; };
+    std::vector<uint32_t> brick_new(nb, VHX_EMPTY), brick_src;
+    for (uint32_t o : old_of) {
+        const uint32_t ty = t.node_type[o];
+        const uint32_t entries = ty == VHX_NODE_LEAF ? 64u : ty == VHX_NODE_UNIFORM_LEAF ? 1u : 0u;
+        for (uint32_t s = 0; s < entries; ++s) {
+            const uint32_t e = t.node_children[(size_t)o * 64 + s];
+            if (!parted(e)) continue;
+            if (e >= nb || brick_new[e] != VHX_EMPTY) return VHX_E_TREE_INVALID_STRUCTURE;
+            brick_new[e] = (uint32_t)brick_src.size();
+            brick_src.push_back(e);
+        }
+    }
+    std::unique_ptr<vhx_flat> f(new vhx_flat());
+    f->size = t.boxtree_size;
+    f->brick_dim = t.brick_dim;
+    const size_t n = old_of.size();
+    f->node_type.resize(n);
+    f->node_ocbits.resize(n);
+    f->node_children.resize(n * 64);
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t o = old_of[i], ty = t.node_type[o];
+        f->node_type[i] = ty;
+        f->node_ocbits[i] = t.node_ocbits[o];
+        const uint32_t entries = ty == VHX_NODE_LEAF ? 64u : ty == VHX_NODE_UNIFORM_LEAF ? 1u : 0u;
+        for (uint32_t s = 0; s < 64; ++s) {
+            uint32_t e = t.node_children[(size_t)o * 64 + s];
+            if (ty == VHX_NODE_INTERNAL) {
+                if (e != VHX_EMPTY) e = new_of[e];
+            } else if (s < entries && parted(e)) {
+                e = brick_new[e];
+            }
+            f->node_children[i * 64 + s] = e;
+        }
+    }
+    f->brick_count = (uint32_t)brick_src.size();
+    f->voxel_count = (uint64_t)brick_src.size() * n3;
+    f->voxels.reset(new uint32_t[std::max<uint64_t>(f->voxel_count, 1)]);
+    for (size_t j = 0; j < brick_src.size(); ++j)
+        std::memcpy(&f->voxels[j * n3], t.voxels + (size_t)brick_src[j] * n3, n3 * 4);
+    f->solid_values.assign(t.solid_values, t.solid_values + t.solid_count);
+    f->color_palette.assign(t.color_palette, t.color_palette + t.color_count);
+    f->data_palette.assign(t.data_palette, t.data_palette + t.data_count);
+    *out = f.release();
+    return VHX_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- C ABI
 extern "C" {
 
@@ -809,6 +887,16 @@ int vhx_flat_desc(const vhx_flat *f, vhx_tree_desc *d) {
     d->color_palette = f->color_palette.data();
     d->data_palette = f->data_palette.data();
     return VHX_OK;
+}
+int vhx_flat_compact(const vhx_tree_desc *tree, vhx_flat **out) {
+    if (!out) return VHX_E_INVALID_ARG;
+    *out = nullptr;
+    if (!tree) return VHX_E_INVALID_ARG;
+    try {
+        return compact_image(*tree, out);
+    } catch (const std::bad_alloc &) {
+        return VHX_E_CAPACITY;
+    }
 }
 void vhx_flat_free(vhx_flat *f) { delete f; }
 

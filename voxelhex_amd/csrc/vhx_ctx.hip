@@ -232,7 +232,9 @@ void vhx_destroy(vhx_ctx *c) {
                       &c->shadow_args, &c->tail_list[0], &c->tail_list[1], &c->tail_mask, &c->build.occ, &c->build.rank,
                       &c->build.first, &c->build.part, &c->build.table, &c->build.ctl, &c->build.grid,
                       &c->build.simp, &c->sky, &c->query, &c->edit.oldn, &c->edit.aft, &c->edit.need,
-                      &c->edit.rank, &c->edit.nmask, &c->edit.first, &c->edit.ctl})
+                      &c->edit.rank, &c->edit.nmask, &c->edit.first, &c->edit.ctl, &c->compact.new_of,
+                      &c->compact.old_of, &c->compact.nmask, &c->compact.nrank, &c->compact.bmask,
+                      &c->compact.bfirst, &c->compact.bnew, &c->compact.bsrc, &c->compact.ctl})
         if (b->ptr) (void)hipFree(b->ptr);
     if (c->tail_stream) {
         (void)hipStreamSynchronize(c->tail_stream);

@@ -6,7 +6,8 @@
 //   k_child_rec       DevTree::child_rec (brick_dim <= 4): one record per child entry
 //   k_scatter_ranges  ranged writes: staged pieces copied to their device addresses
 // Host side: upload (vhx_upload_tree*, receive_tree), ranged updates (vhx_update_range(s)), node MIPs, read-back of the
-// derived layout, content-preserving growth of the buffers for vhx_write_dense (grow_tree), vhx_tree_orphans. Launches no kernel of another unit; the trace unit (vhx_device.hip) calls refresh_child_rec.
+// derived layout, content-preserving growth of the buffers for vhx_write_dense (grow_tree), the buffer swap of
+// vhx_compact_tree (alloc_fresh_tree, adopt_fresh_tree), vhx_tree_orphans. Launches no kernel of another unit; the trace unit (vhx_device.hip) calls refresh_child_rec.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -283,6 +284,77 @@ int vhx::finish_upload(vhx_ctx *c) {
     }
     VHX_HIP(c, hipStreamSynchronize(c->stream));
     c->tree->uploaded = true;
+    return VHX_OK;
+}
+
+uint64_t vhx::raw_bytes(const vhx_tree_desc &counts, int id) {
+    const uint64_t b = elem_count(counts, id) * elem_size(id);
+    return b ? b : 16;
+}
+
+void vhx::free_fresh_tree(FreshTree *f) {
+    DevBuf *all[10] = {&f->raw[0], &f->raw[1], &f->raw[2], &f->raw[3], &f->raw[4],
+                       &f->raw[5], &f->raw[6], &f->hdr,    &f->brick_occ, &f->child_rec};
+    for (DevBuf *b : all) {
+        if (b->ptr) (void)hipFree(b->ptr);
+        *b = DevBuf{};
+    }
+}
+
+int vhx::alloc_fresh_tree(vhx_ctx *c, const vhx_tree_desc &counts, FreshTree *f) {
+    const TreeStore &ts = *c->tree;
+    struct Want {
+        DevBuf *b;
+        uint64_t bytes;
+    } want[10];
+    uint32_t n = 0;
+    for (int id = 0; id < 7; ++id) {
+        const bool palette = id >= VHX_BUF_SOLID_VALUES;
+        if (palette && ts.raw[id].bytes <= raw_bytes(counts, id)) continue;  // kept as it is
+        want[n++] = {&f->raw[id], raw_bytes(counts, id)};
+    }
+    const uint64_t occ_bytes = (uint64_t)counts.brick_count * ts.occ_words * 8;
+    want[n++] = {&f->hdr, (uint64_t)counts.node_count * 16};
+    want[n++] = {&f->brick_occ, occ_bytes ? occ_bytes : 16};
+    if (has_child_rec(c)) want[n++] = {&f->child_rec, (uint64_t)counts.node_count * 64 * 16};
+    for (uint32_t i = 0; i < n; ++i) {
+        const hipError_t e = hipMalloc(&want[i].b->ptr, want[i].bytes);
+        if (e != hipSuccess) {
+            want[i].b->ptr = nullptr;
+            free_fresh_tree(f);
+            (void)hipGetLastError();
+            return fail(c, VHX_E_HIP, std::string("vhx_compact_tree: hipMalloc: ") + hipGetErrorString(e));
+        }
+        want[i].b->bytes = want[i].bytes;
+    }
+    return VHX_OK;
+}
+
+int vhx::adopt_fresh_tree(vhx_ctx *c, const vhx_tree_desc &counts, FreshTree *f) {
+    TreeStore &ts = *c->tree;
+    for (int id = VHX_BUF_SOLID_VALUES; id < 7; ++id) {
+        const uint64_t used = elem_count(counts, id) * elem_size(id);
+        if (f->raw[id].ptr && used)
+            VHX_HIP(c, hipMemcpyAsync(f->raw[id].ptr, ts.raw[id].ptr, used, hipMemcpyDeviceToDevice, c->stream));
+    }
+    for (int id = 0; id < 7; ++id)
+        if (f->raw[id].ptr) std::swap(ts.raw[id], f->raw[id]);
+    std::swap(ts.hdr, f->hdr);
+    std::swap(ts.brick_occ, f->brick_occ);
+    if (has_child_rec(c)) std::swap(ts.child_rec, f->child_rec);
+    ts.desc.node_count = counts.node_count;
+    ts.desc.brick_count = counts.brick_count;
+    ts.orphan_nodes = ts.orphan_bricks = 0;
+    int rc = rebuild_hdr(c, 0, counts.node_count);
+    if (!rc && has_child_rec(c)) {
+        ts.child_rec_stale = true;
+        rc = refresh_child_rec(c);
+    }
+    // the frames in flight read the old buffers, now in *f: c's stream waits for them (write_begin)
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    free_fresh_tree(f);
+    if (rc) return rc;
+    VHX_HIP(c, e);
     return VHX_OK;
 }
 

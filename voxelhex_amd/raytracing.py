@@ -365,7 +365,8 @@ class Raytracer:
         the box becomes the grid's, alpha 0 clears; "insert": grid voxels with alpha 0 leave the tree as it is. `grid` is
         a uint32 numpy array (copied to the device first) or a contiguous int32 / uint32 torch tensor on this context's
         device, read in place (torch's current stream is synchronised before the call). Owner context only; the call
-        returns when the tree is ready."""
+        returns when the tree is ready. Slots are never reused: orphans() counts the unlinked ones and compact() drops
+        them."""
         modes = {"replace": N.VHX_WRITE_REPLACE, "insert": N.VHX_WRITE_INSERT}
         box = N.DenseIn()
         box.ox, box.oy, box.oz = (int(v) for v in origin)
@@ -394,9 +395,22 @@ class Raytracer:
 
     def orphans(self):
         """vhx_tree_orphans: (nodes, bricks) that write_dense / fill_box unlinked since the last upload or build; their
-        slots are not reused (read_dense + build_dense compacts)."""
+        slots are not reused (compact() drops them)."""
         n, b = ctypes.c_uint32(), ctypes.c_uint32()
         self._check(N.lib().vhx_tree_orphans(self._h, ctypes.byref(n), ctypes.byref(b)))
+        return n.value, b.value
+
+    def compact(self):
+        """vhx_compact_tree: rewrites the resident tree on the device without its unreachable node and brick slots and
+        in the builders' numbering (download() then equals download().compacted() of before, bit for bit); every get,
+        read_dense and trace result stays as it was, the buffers shrink (device_bytes) and orphans() is (0, 0). Returns
+        (nodes_dropped, bricks_dropped). Out of place: the peak device memory is the old tree plus the new one. Owner
+        context only, not while node MIPs are set, and not under a streamed view (its host cache keeps slot numbers);
+        a refused call leaves the tree as it was."""
+        n, b = ctypes.c_uint32(), ctypes.c_uint32()
+        self._check(N.lib().vhx_compact_tree(self._h, ctypes.byref(n), ctypes.byref(b)))
+        if not isinstance(self._tree, _BuiltOnDevice):
+            self._tree = _BuiltOnDevice()  # no longer the uploaded FlatTree: upload() of it must upload again
         return n.value, b.value
 
     def update_range(self, buffer_id, elem_offset, values):
