@@ -13,7 +13,8 @@ from collections import defaultdict
 rows = list(csv.DictReader(open(sys.argv[1])))
 skip, steps = int(sys.argv[2]), int(sys.argv[3])
 frame_k = ("k_trace_primary<false", "k_trace_primary_batch<", "k_trace_queue<false", "k_count_flags", "k_scan_counts",
-           "k_emit_flags", "k_gather_chunks", "k_put_queue_args", "k_scan_sums", "k_classify_sky")
+           "k_emit_flags", "k_gather_chunks", "k_put_queue_args", "k_scan_sums", "k_classify_sky", "k_classify_blocks",
+           "k_emit_worklist")
 ks = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].replace("void ", ""),
              int(r.get("Grid_Size_X") or r.get("Grid_Size") or 0)) for r in rows)
 # pass-0 dispatches with the frames each opens: 1, or a batch's K (grid / (256 x FRAME_BLOCKS), FRAME_BLOCKS = 32400

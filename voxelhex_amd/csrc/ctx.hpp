@@ -239,12 +239,15 @@ struct vhx_ctx {
     // runs), 100 frames 0.4914 against 0.5041-0.5085, config 4 1.786-1.794 against 1.863-1.879, the moving camera
     // 0.721-0.723 against 0.737-0.740 (profiles/r06/finter/)
     bool frame_interleave = true;
-    // batch pass 0 (whole frames, no fused shadows): k_classify_sky marks the 16x16 blocks whose every pixel is certain
-    // to miss the root cube (skyblock.hpp) in `sky`, one byte per (frame, raster block), on the context's stream ahead
-    // of pass 0; a marked block's workgroup writes its miss records and leaves before the occupancy-table fill, the
-    // barrier and the per-lane sky test (tune "skyblocks"; profiles/r08/skyblocks/)
+    // batch pass 0 (whole frames in list order, no fused shadows): k_classify_blocks and k_emit_worklist partition the
+    // launch's workgroup indices in `work`, on the context's stream ahead of pass 0 -- the blocks with a pixel that may
+    // enter the tree first, in the order of the lists, then the 16x16 blocks whose every pixel is certain to miss the
+    // root cube (skyblock.hpp), with both counts on the device. The first workgroups of the launch trace the tree
+    // blocks, the next ones write a sky block's miss records with one wave each, the rest end at once, and the
+    // compaction that follows covers the tree blocks' lists only (tune "skyblocks": 0 = every block takes the full
+    // path; profiles/r08/skyblocks/, profiles/r13/worklist/)
     bool skyblocks = true;
-    DevBuf sky;
+    DevBuf work;
     // passes before save_from keep no state: the rays they abandon are traced again from scratch by pass save_from,
     // which saves (tune "save_from"; 0 = every budgeted pass saves)
     uint32_t save_from = 0;

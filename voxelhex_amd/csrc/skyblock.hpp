@@ -1,6 +1,6 @@
 // Sky blocks: whether every pixel of a pixel rectangle of a glass-camera frame is certain to miss the root cube on the
 // exact path -- primary_ray (vhx_device.hip) followed by the slab test of Trav::begin (trace.hpp). Pass 0 of a batch
-// asks this once per 16x16 block before the block's workgroup starts (k_classify_sky); a block that is sky in every
+// asks this once per 16x16 block before the block's workgroup starts (k_classify_blocks); a block that is sky in every
 // pixel writes its miss records and leaves without the traversal prologue.
 //
 // Self-contained: no includes beyond <stdint.h>, only + - * / and comparisons in double precision (IEEE, no fused

@@ -231,7 +231,7 @@ void vhx_destroy(vhx_ctx *c) {
                       &c->flags, &c->qargs, &c->state, &c->stateq, &c->upd, &c->prepass_depth, &c->batch_args, &c->scan_part,
                       &c->shadow_args, &c->tail_list[0], &c->tail_list[1], &c->tail_mask, &c->build.occ, &c->build.rank,
                       &c->build.first, &c->build.part, &c->build.table, &c->build.ctl, &c->build.grid,
-                      &c->build.simp, &c->sky, &c->query, &c->edit.oldn, &c->edit.aft, &c->edit.need,
+                      &c->build.simp, &c->work, &c->query, &c->edit.oldn, &c->edit.aft, &c->edit.need,
                       &c->edit.rank, &c->edit.nmask, &c->edit.first, &c->edit.ctl, &c->compact.new_of,
                       &c->compact.old_of, &c->compact.nmask, &c->compact.nrank, &c->compact.bmask,
                       &c->compact.bfirst, &c->compact.bnew, &c->compact.bsrc, &c->compact.ctl})
@@ -349,7 +349,7 @@ static int apply_tuning(vhx_ctx *c, const std::string &key, const std::string &v
     } else if (key == "finter") {  // batches: pass-0 blocks of the frames interleaved (1) or frame-major (0)
         if (!parse_u32(val, x) || x > 1) return bad();
         c->frame_interleave = x != 0;
-    } else if (key == "skyblocks") {  // batches: all-sky blocks classified ahead of pass 0 (1) or every block alike (0)
+    } else if (key == "skyblocks") {  // batches: pass 0 over a worklist, tree blocks first, all-sky blocks last (1) or every block alike (0)
         if (!parse_u32(val, x) || x > 1) return bad();
         c->skyblocks = x != 0;
     } else if (key == "stage_slots") {  // batch staging ring slots in use (1 = wait for the previous batch's copy)

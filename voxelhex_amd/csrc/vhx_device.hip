@@ -6,7 +6,8 @@
 //                    (examples/gpu_render.rs:196-257, benches/performance.rs:29-66) traced with get_by_ray semantics
 //                    (src/raytracing/cpu.rs:296-458); replaces the WGSL `update` kernel dispatched by
 //                    VhxRenderNode::run (src/raytracing/bevy/pipeline/mod.rs:96-155)
-//   k_classify_sky   a batch's sky mask: the 16x16 blocks whose every pixel misses the root cube (skyblock.hpp)
+//   k_classify_blocks, k_emit_worklist  a batch's pass-0 worklist: its tree blocks in logical order, then the 16x16
+//                    blocks whose every pixel misses the root cube (skyblock.hpp)
 //   k_trace_rays     pass 0 of an explicit ray batch (BoxTree::get_by_ray over many rays)
 //   k_trace_queue    the queue passes: the rays an earlier pass abandoned at its step budget, and shadow rays
 //   k_trace_tail, k_tail_mask  the early tail of a lone frame
@@ -49,8 +50,9 @@ struct OutD {
 };
 
 // examples/gpu_render.rs:199, 236-251
+#define VHX_MISS_RGBA (128u | (128u << 8) | (128u << 16) | (255u << 24))
 __device__ __forceinline__ uint32_t shade(const DevTree &t, const HitOut &h) {
-    if (!h.hit) return 128u | (128u << 8) | (128u << 16) | (255u << 24);
+    if (!h.hit) return VHX_MISS_RGBA;
     const uint32_t ci = h.value & 0xFFFFu;
     if (ci == 0xFFFFu || ci >= t.color_count) return 255u << 24;
     const uint32_t c = t.color[ci];
@@ -83,6 +85,39 @@ __device__ __forceinline__ void store(const DevTree &t, const OutD &o, uint64_t 
     if (o.depth) o.depth[i] = h.hit ? vlen(vsub(mk(h.ix, h.iy, h.iz), org)) : __builtin_huge_valf();
     if (o.rgba) o.rgba[i] = shade(t, h);
     if (o.bytes) o.bytes[i] = h.bytes;
+}
+
+// The miss record of a whole 16x16 block (bx, by) of a W x H framebuffer frame, written by one wave: what store()
+// writes for a miss, to every non-null plane, for the block's pixels inside the frame only. Lane l covers pixels
+// 4 (l & 3) .. + 3 of the block's row l >> 2: one 16-byte store per one-word plane and three per three-word plane where
+// the four pixels lie inside the frame and the plane's address there is 16-byte aligned (a frame width that is a
+// multiple of 4 on an aligned array), else word by word.
+template <int WORDS, class T, class T4>
+__device__ __forceinline__ void fill_miss(T *plane, uint64_t i, uint32_t npx, T v) {
+    if (!plane) return;
+    T *a = plane + WORDS * i;
+    if (npx == 4u && ((uintptr_t)a & 15u) == 0u) {
+        T4 v4;
+        v4.x = v4.y = v4.z = v4.w = v;
+#pragma unroll
+        for (int k = 0; k < WORDS; ++k) ((T4 *)a)[k] = v4;
+    } else {
+        for (uint32_t k = 0; k < WORDS * npx; ++k) a[k] = v;
+    }
+}
+__device__ __forceinline__ void store_miss_block(const OutD &o, uint32_t bx, uint32_t by, uint32_t W, uint32_t H) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t x = bx * 16u + (lane & 3u) * 4u, y = by * 16u + (lane >> 2);
+    if (x >= W || y >= H) return;
+    const uint64_t i = (uint64_t)y * W + x;
+    const uint32_t npx = W - x < 4u ? W - x : 4u;
+    fill_miss<1, uint32_t, uint4>(o.value, i, npx, VHX_EMPTY);
+    fill_miss<1, uint32_t, uint4>(o.cell, i, npx, VHX_EMPTY);
+    fill_miss<3, uint32_t, uint4>(o.voxel, i, npx, VHX_EMPTY);
+    fill_miss<3, float, float4>(o.impact, i, npx, 0.0f);
+    fill_miss<3, float, float4>(o.normal, i, npx, 0.0f);
+    fill_miss<1, float, float4>(o.depth, i, npx, __builtin_huge_valf());
+    fill_miss<1, uint32_t, uint4>(o.rgba, i, npx, VHX_MISS_RGBA);
 }
 
 // benches/performance.rs:54-61 (glass) and examples/gpu_render.rs:203-224 (inverse VP, glam op order)
@@ -139,24 +174,6 @@ __device__ __forceinline__ bool glass_clear_miss(const CamD &c, uint32_t px, uin
     if (!safe || !__builtin_isfinite(tmin) || !__builtin_isfinite(tmax)) return false;
     const float m = 1e-5f * __builtin_fmaxf(__builtin_fabsf(tmin), __builtin_fabsf(tmax));
     return tmax < -m || tmin - tmax > m;
-}
-
-// The sky mask of a batch's pass 0 (vhx_ctx::skyblocks): one thread per (frame, 16x16 block), block_is_sky
-// (skyblock.hpp) on the block's pixels inside the frame; mask[f * blocks_x * blocks_y + by * blocks_x + bx] = 1 where
-// every pixel of the block misses the root cube on the exact path. A byte per block: k_trace_primary_batch reads its
-// entry's word with a scalar load.
-__global__ void __launch_bounds__(256) k_classify_sky(const CamD *__restrict__ cams, uint32_t nfr, uint32_t blocks_x,
-                                                      uint32_t blocks_y, uint32_t tree_size,
-                                                      uint8_t *__restrict__ mask) {
-    const uint32_t nb = blocks_x * blocks_y;
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= nfr * nb) return;
-    const uint32_t f = i / nb, b = i - f * nb, by = b / blocks_x, bx = b - by * blocks_x;
-    const CamD &c = cams[f];
-    const SkyCam s{c.model, c.width, c.height, {c.ox, c.oy, c.oz}, {c.blx, c.bly, c.blz}, {c.rx, c.ry, c.rz},
-                   {c.ux, c.uy, c.uz}, c.pw, c.ph};
-    const uint32_t x1 = min(bx * 16u + 15u, c.width - 1u), y1 = min(by * 16u + 15u, c.height - 1u);
-    mask[i] = block_is_sky(s, tree_size, bx * 16u, by * 16u, x1, y1) ? 1 : 0;
 }
 
 // ------------------------------------------------------------------------------------------- multi-pass scheduling
@@ -861,7 +878,7 @@ struct BatchGrid {
     UDiv split;       // workgroup -> (frame, frame block): by nfr (interleaved) or by nblocks_frame (frame-major)
     UDiv ltx, bx;     // frame block -> block coordinates: by lo.tx (list order) or by blocks_x (row-major)
     UDiv bpt, bpx, tiles_x;  // tile sets: by TileB's bpt, bpx and tiles_x
-    // sky blocks (the kernel's `sky` mask, k_classify_sky): the frame's 16x16 raster blocks and the frames' common size
+    // the worklist (k_classify_blocks, the kernel's `work`): the frame's 16x16 raster blocks and the frames' common size
     uint32_t sbx, sby, W, H;
 };
 static BatchGrid batch_grid(uint32_t nblocks, uint32_t nfr, uint32_t nblocks_frame, uint32_t blocks_x, const PassQ &q,
@@ -898,6 +915,89 @@ __device__ __forceinline__ void list_block(const ListOrder &lo, const UDiv &ltx,
     bx = ((tb - ty * lo.tx) << lo.tbl) + compact_bits(m);
     by = (ty << lo.tbl) + compact_bits(m >> 1);
 }
+// xcd_block over the first n workgroups of the launch, n read on the device (the worklist's tree part, n < 2^31)
+__device__ __forceinline__ uint32_t xcd_block_n(uint32_t bid, uint32_t n, uint32_t G, const BatchGrid &g) {
+    if (G == 0u) return bid;
+    uint32_t full;  // n / 8G * 8G
+    if (g.xshift != ~0u) full = g.xshift >= 29u ? 0u : (n >> (g.xshift + 3u)) << (g.xshift + 3u);
+    else full = udiv(n >> 3, g.xg) * 8u * G;
+    if (bid >= full) return bid;
+    const uint32_t x = bid & 7u, k = bid >> 3;
+    if (g.xshift != ~0u) return ((((k >> g.xshift) << 3) + x) << g.xshift) + (k & (G - 1u));
+    const uint32_t kq = udiv(k, g.xg);
+    return (kq * 8u + x) * G + (k - kq * G);
+}
+// a logical workgroup index of a batch's pass 0 -> its frame and frame block (interleaved or frame-major)
+__device__ __forceinline__ void batch_split(uint32_t bid, uint32_t finter, uint32_t nblocks_frame, const BatchGrid &g,
+                                            uint32_t &f, uint32_t &sb) {
+    const uint32_t bq = udiv(bid, g.split);
+    f = finter ? bid - bq * g.nfr : bq;
+    sb = finter ? bq : bid - bq * nblocks_frame;
+}
+
+// The worklist of a batch's pass 0 (vhx_ctx::skyblocks; whole frames in list order without fused shadows): the
+// launch's logical workgroup indices -- position p is frame block sb of frame f after the frame interleave, in list
+// order: the order of the lists and of the pass-1 queue -- partitioned. work[WORK_HDR ...] holds first the ntree
+// blocks with a pixel that may enter the tree, ascending in p, then the nsky blocks inside the frame whose every pixel
+// misses the root cube on the exact path (block_is_sky, skyblock.hpp); the blocks of the list order's padding past
+// the frame are in neither part. work[0] = ntree, work[1] = ntree + nsky, work[2] = 256 ntree (the pass-0 lists'
+// extent in rays, the device-side length its compaction takes).
+// k_classify_blocks: one thread per position; per wave of 64 positions the two ballots, per workgroup of 256 their
+// counts (tree counts at counts[g], sky counts at counts[ng + g]: one exclusive scan over 2 ng counts places the sky
+// part behind the tree part and leaves ntree at offsets[ng], the sum at work[1]). k_emit_worklist, on the same grid,
+// writes the entries.
+#define WORK_HDR 64u
+__global__ void __launch_bounds__(256) k_classify_blocks(const CamD *__restrict__ cams, BatchGrid bg, ListOrder lo,
+                                                         uint32_t nblocks_frame, uint32_t finter, uint32_t nblocks,
+                                                         uint32_t tree_size, uint64_t *__restrict__ masks,
+                                                         uint32_t *__restrict__ counts) {
+    __shared__ uint32_t s_cnt[8];
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    bool tree = false, sky = false;
+    if (p < nblocks) {
+        uint32_t f, sb, bx, by;
+        batch_split(p, finter, nblocks_frame, bg, f, sb);
+        list_block(lo, bg.ltx, sb, bx, by);
+        if (bx < bg.sbx && by < bg.sby) {
+            const CamD &c = cams[f];
+            const SkyCam s{c.model, c.width, c.height, {c.ox, c.oy, c.oz}, {c.blx, c.bly, c.blz}, {c.rx, c.ry, c.rz},
+                           {c.ux, c.uy, c.uz}, c.pw, c.ph};
+            const uint32_t x1 = min(bx * 16u + 15u, c.width - 1u), y1 = min(by * 16u + 15u, c.height - 1u);
+            sky = block_is_sky(s, tree_size, bx * 16u, by * 16u, x1, y1);
+            tree = !sky;
+        }
+    }
+    const uint64_t mt = __ballot(tree), ms = __ballot(sky);
+    const uint32_t w = p >> 6, wave = threadIdx.x >> 6;  // (the ballots hold four words per workgroup of the grid)
+    if ((threadIdx.x & 63u) == 0u) {
+        masks[2u * w] = mt;
+        masks[2u * w + 1u] = ms;
+        s_cnt[wave] = (uint32_t)__popcll(mt);
+        s_cnt[4u + wave] = (uint32_t)__popcll(ms);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        counts[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        counts[gridDim.x + blockIdx.x] = s_cnt[4] + s_cnt[5] + s_cnt[6] + s_cnt[7];
+    }
+}
+__global__ void __launch_bounds__(256) k_emit_worklist(const uint64_t *__restrict__ masks,
+                                                       const uint32_t *__restrict__ offsets,
+                                                       uint32_t *__restrict__ work) {
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x, w = p >> 6, lane = threadIdx.x & 63u;
+    if (p == 0u) {
+        work[0] = offsets[gridDim.x];
+        work[2] = offsets[gridDim.x] * 256u;
+    }
+    const uint64_t mt = masks[2u * w], ms = masks[2u * w + 1u], below = (1ull << lane) - 1ull;
+    uint32_t ot = offsets[blockIdx.x], os = offsets[gridDim.x + blockIdx.x];
+    for (uint32_t v = blockIdx.x * 4u; v < w; ++v) {  // the workgroup's waves ahead of this one
+        ot += (uint32_t)__popcll(masks[2u * v]);
+        os += (uint32_t)__popcll(masks[2u * v + 1u]);
+    }
+    if ((mt >> lane) & 1ull) work[WORK_HDR + ot + (uint32_t)__popcll(mt & below)] = p;
+    if ((ms >> lane) & 1ull) work[WORK_HDR + os + (uint32_t)__popcll(ms & below)] = p;
+}
 
 // The workgroup's position, frame and frame block are the same in every lane by construction; readfirstlane says so
 // to the compiler, which then keeps them, everything derived from them (the block's coordinates, the tile, the
@@ -916,16 +1016,44 @@ __global__ void __launch_bounds__(256) VHX_BATCH_ATTR k_trace_primary_batch(DevT
                                                              uint32_t blocks_x, uint32_t npix, PassQ q, BatchGrid bg,
                                                              ListOrder lo = ListOrder{}, TileB tb = TileB{},
                                                              const uint32_t *__restrict__ starts = nullptr,
-                                                             const uint32_t *__restrict__ sky = nullptr) {
+                                                             const uint32_t *__restrict__ work = nullptr) {
     __shared__ uint64_t occ_tab[OCC_TAB_WORDS];
     zero_ctl(q.zero);
-    const uint32_t bid = __builtin_amdgcn_readfirstlane(xcd_block(blockIdx.x, q.xcd_group, bg));
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    // bid: the workgroup's logical index (frame and frame block); pos: its position among the pass's lists
+    uint32_t bid, pos;
+    if (!FUSE && work) {
+        // The worklist (k_classify_blocks): the launch's first ntree workgroups trace the tree blocks, XCD-dealt among
+        // themselves, and list their rays at the block's rank -- the lists in position order are those of the whole
+        // launch without its empty ones; the next nsky workgroups write a sky block's miss records, one wave of each
+        // (no occupancy table, no barrier, no camera, no list entry); the rest, the list order's padding, end here.
+        // Tree work starts first and the fills are the launch's tail. Every branch is workgroup-uniform (scalar).
+        const uint32_t ntree = work[0], nall = work[1];
+        if (blockIdx.x >= nall) return;
+        if (blockIdx.x >= ntree) {
+            if (wave != 0u) return;
+            uint32_t f, sb, bx, by;
+            batch_split(__builtin_amdgcn_readfirstlane(work[WORK_HDR + blockIdx.x]), q.finter, nblocks_frame, bg, f, sb);
+            list_block(lo, bg.ltx, sb, bx, by);
+            // the plane pointers in scalar loads issued together, one wait (the empty asm keeps the compiler from
+            // reading each behind the branch on the one before)
+            const OutD out = outs[f];
+            asm volatile("" ::"s"(out.value), "s"(out.cell), "s"(out.voxel), "s"(out.rgba), "s"(out.impact),
+                         "s"(out.normal), "s"(out.depth));
+            store_miss_block(out, bx, by, bg.W, bg.H);
+            return;
+        }
+        pos = __builtin_amdgcn_readfirstlane(xcd_block_n(blockIdx.x, ntree, q.xcd_group, bg));
+        bid = __builtin_amdgcn_readfirstlane(work[WORK_HDR + pos]);
+    } else {
+        pos = bid = __builtin_amdgcn_readfirstlane(xcd_block(blockIdx.x, q.xcd_group, bg));
+    }
     // frame-major (all of frame 0's blocks, then frame 1's, ...) or interleaved (block sb of every frame in turn: the
     // frames' rays through one screen region run together and share the caches)
-    const uint32_t bq = udiv(bid, bg.split);
-    const uint32_t f = __builtin_amdgcn_readfirstlane(q.finter ? bid - bq * bg.nfr : bq);
-    const uint32_t sb = __builtin_amdgcn_readfirstlane(q.finter ? bq : bid - bq * nblocks_frame);
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    uint32_t f, sb;
+    batch_split(bid, q.finter, nblocks_frame, bg, f, sb);
+    f = __builtin_amdgcn_readfirstlane(f);
+    sb = __builtin_amdgcn_readfirstlane(sb);
     uint32_t px = 0, py = 0, local;
     if (!tb.T) {
         uint32_t bx, by;
@@ -938,33 +1066,6 @@ __global__ void __launch_bounds__(256) VHX_BATCH_ATTR k_trace_primary_batch(DevT
             bx = sb - by * blocks_x;
             px = bx * 16u + (wave & 1u) * 8u + (lane & 7u);
             py = by * 16u + (wave >> 1) * 8u + (lane >> 3);
-        }
-        // Sky blocks (vhx_ctx::skyblocks; whole frames without fused shadows -- tile sets and the FUSE instantiations
-        // keep the full path for every block): a block that k_classify_sky marked, or a block of the list order's
-        // padding past the frame, holds no ray that enters the tree. Its workgroup writes the miss record of every pixel
-        // through the same store() and its flags or empty lists, and ends: no occupancy table, no barrier, no camera, no
-        // per-lane sky test. The branch is workgroup-uniform (scalar), ahead of the only barrier. The block's mask word
-        // and outs[f] are read together, so the wave waits for one scalar round trip (the empty asm keeps the compiler
-        // from moving the second load behind the branch; a tree block drops the pointers again).
-        if (!FUSE && sky) {
-            const bool inside = bx < bg.sbx && by < bg.sby;
-            const uint32_t mi = inside ? f * (bg.sbx * bg.sby) + by * bg.sbx + bx : 0u;
-            const uint32_t word = sky[mi >> 2];
-            const OutD out = outs[f];
-            asm volatile("" ::"s"(word), "s"(out.value), "s"(out.cell), "s"(out.voxel), "s"(out.rgba), "s"(out.impact),
-                         "s"(out.normal), "s"(out.depth));
-            if (!inside || ((word >> ((mi & 3u) * 8u)) & 1u) != 0u) {
-                local = py * bg.W + px;
-                if (px < bg.W && py < bg.H) {
-                    HitOut h;
-                    h.hit = false;
-                    h.bytes = 0;
-                    store(t, out, local, mk(0.0f, 0.0f, 0.0f), h);
-                    if (q.flags) q.flags[(uint64_t)f * npix + local] = 0;
-                }
-                if ((lo.tx || lo.tl) && q.tmp) wave_append(false, 0u, q.tmp, q.counts, bid * 4u + wave);
-                return;
-            }
         }
     }
     fill_occ_tab(occ_tab);
@@ -1002,7 +1103,7 @@ __global__ void __launch_bounds__(256) VHX_BATCH_ATTR k_trace_primary_batch(DevT
         } else {
             primary_ray(cam, px, py, o, d);
             done = get_by_ray<false, BD>(t, occ_tab, o, d, h, q.budget, q.state,
-                                         q.qmode ? (bid * 4u + wave) * 64u : (uint32_t)idx, false, 0.0f, q.sparse,
+                                         q.qmode ? (pos * 4u + wave) * 64u : (uint32_t)idx, false, 0.0f, q.sparse,
                                          nullptr, 0, q.qmode != 0);
         }
         if (done) {
@@ -1016,7 +1117,7 @@ __global__ void __launch_bounds__(256) VHX_BATCH_ATTR k_trace_primary_batch(DevT
     }
     // every entry gets its flag (a tile set's entries past the frame edge or past a smaller set's tiles: 0)
     if (q.flags && entry) q.flags[idx] = done ? 0 : 1;
-    if ((lo.tx || lo.tl) && q.tmp) wave_append(!done, (uint32_t)idx | tag, q.tmp, q.counts, bid * 4u + wave);
+    if ((lo.tx || lo.tl) && q.tmp) wave_append(!done, (uint32_t)idx | tag, q.tmp, q.counts, pos * 4u + wave);
 }
 
 template <bool COUNT, int BD, bool MIP = false>
@@ -1630,6 +1731,9 @@ struct QueueRun {
     uint32_t order_w = 0, order_h = 0;  // P0_FLAGS: the frame in whose queue order (c->qorder) the flags are compacted
     uint32_t frames = 1;                // frames of a batch
     bool qm = false;                    // queue-state mode (queue_state_mode)
+    // P0_ORDERED behind a worklist: the extent of pass 0's lists in rays, 256 per tree block, read on the device (the
+    // compaction covers what was traced; null: all of nblocks0)
+    const uint32_t *n0 = nullptr;
 };
 
 // Queue passes first..npass-1: pass p re-traces the queue of pass p-1 (pass 0's queue, for first == 0, is the list
@@ -1650,7 +1754,7 @@ static int launch_queue_passes(vhx_ctx *c, const DevTree &t, const QueueRun &r) 
             if ((rc = compact_flags<false>(c, c->flags.ptr, npos, ord, ctl, queue0))) return rc;
             if ((rc = sort_segments(c, 1, npass, queue0, ctl, r.nout))) return rc;
         } else if (r.pass0 == P0_ORDERED) {  // per-wave lists (wave_append): 4 chunks of 64 per workgroup
-            rc = compact_chunks(c, (uint32_t)(r.nblocks0 * 4), nullptr, 64, 64, queue0, ctl, r.nblocks0 * 4, r.qm);
+            rc = compact_chunks(c, (uint32_t)(r.nblocks0 * 4), r.n0, 64, 64, queue0, ctl, r.nblocks0 * 4, r.qm);
             if (!rc) rc = sort_segments(c, 1, npass, queue0, ctl, r.nout);
         } else {
             rc = compact_chunks(c, (uint32_t)r.nblocks0, nullptr, 256, 256, queue0, ctl, r.nblocks0);
@@ -2183,10 +2287,6 @@ static int trace_batch(vhx_ctx *c, const vhx_camera *cams, uint32_t n, const vhx
     if (T) std::memcpy((uint8_t *)P->ptr + cam_bytes + out_bytes, starts, (size_t)n * 4);
     uint32_t npass = 1;
     if ((rc = prepare_passes(c, nout, nblocks, npass, false, n > 1))) return rc;
-    // the sky mask: a byte per frame and raster block, read by words (grown only when a larger batch comes: sized here,
-    // ahead of the launches, like every other per-trace buffer)
-    const bool sky = c->skyblocks && !T;
-    if (sky && (rc = ensure(c, c->sky, ((uint64_t)bx * by * n + 3) & ~3ull))) return rc;
     if ((rc = tr.start()) || (rc = stage_commit(c, *P, c->batch_args, args_bytes))) return rc;
     const CamD *dcams = (const CamD *)c->batch_args.ptr;
     const OutD *douts = (const OutD *)((const uint8_t *)c->batch_args.ptr + cam_bytes);
@@ -2216,22 +2316,36 @@ static int trace_batch(vhx_ctx *c, const vhx_camera *cams, uint32_t n, const vhx
     const PassQ q0 = pass0_q(c, npass, run.pass0, p0.qm);
     // everything the kernel would derive from the grid size, and its divisions, as constants
     BatchGrid bg = batch_grid((uint32_t)run.nblocks0, n, (uint32_t)p0.nbf, bx, q0, p0.lo, tb);
-    const uint32_t *dsky = nullptr;  // null: every block takes the full path
-    if (sky && !p0.fuse) {  // one launch per batch, ahead of pass 0 on the same stream (the FUSE kernels do not read it)
-        const uint32_t nsky = bx * by * n;
-        k_classify_sky<<<(nsky + 255u) / 256u, 256, 0, c->stream>>>(dcams, n, bx, by, t.size, (uint8_t *)c->sky.ptr);
-        dsky = (const uint32_t *)c->sky.ptr;
+    // The worklist (k_classify_blocks): whole frames listed in the list order, without fused shadows. Three launches
+    // ahead of pass 0 on the same stream; the buffer (header, entries, and the build's ballots, counts and offsets)
+    // keeps the upper bound of the launch and grows only when a larger batch comes. The lists' extent, 256 rays per
+    // tree block, must fit the 32 bits of a device-side length; a batch of more (tiny frames by the million) takes the
+    // full path for every block, like skyblocks = 0.
+    const uint32_t *dwork = nullptr;  // null: every block takes the full path
+    if (c->skyblocks && !T && p0.listed && p0.lo.tx && !p0.fuse && ((uint64_t)bx * by * n + 1) * 256 <= 0xFFFFFFFFull) {
+        const uint32_t nb0 = (uint32_t)run.nblocks0, ng = (nb0 + 255u) / 256u;  // the build's grid
+        const uint64_t ent_words = (WORK_HDR + (uint64_t)nb0 + 1) & ~1ull;  // the ballots that follow are 8-byte words
+        if ((rc = ensure(c, c->work, (ent_words + 20ull * ng) * 4))) return rc;
+        uint32_t *work = (uint32_t *)c->work.ptr;
+        uint64_t *masks = (uint64_t *)(work + ent_words);  // two per wave of the grid
+        uint32_t *wcounts = work + ent_words + 16ull * ng, *woffsets = wcounts + 2ull * ng;
         bg.sbx = bx;
         bg.sby = by;
         bg.W = W;
         bg.H = H;
+        k_classify_blocks<<<ng, 256, 0, c->stream>>>(dcams, bg, p0.lo, (uint32_t)p0.nbf, q0.finter, nb0, t.size, masks,
+                                                      wcounts);
+        launch_scan(c, wcounts, 2u * ng, nullptr, 1, woffsets, work + 1, 2ull * ng);
+        k_emit_worklist<<<ng, 256, 0, c->stream>>>(masks, woffsets, work);
+        dwork = work;
+        run.n0 = work + 2;
     }
     int qrc = VHX_OK;
     const bool bd_ok = dispatch_variant(c->tree->desc.brick_dim, false, false, p0.fuse, false, [&](auto bd_tag, auto v) {
         constexpr int BD = decltype(bd_tag)::value;
         constexpr bool FUSE = decltype(v)::FUSE;
         k_trace_primary_batch<BD, FUSE><<<(unsigned)run.nblocks0, 256, 0, c->stream>>>(
-            t, dcams, douts, (uint32_t)p0.nbf, bx, (uint32_t)npix, q0, bg, p0.lo, tb, dstarts, dsky);
+            t, dcams, douts, (uint32_t)p0.nbf, bx, (uint32_t)npix, q0, bg, p0.lo, tb, dstarts, dwork);
         qrc = launch_queue_passes<false, BD, false, FUSE>(c, t, run);
     });
     if (!bd_ok) return fail(c, VHX_E_INVALID_ARG, "unsupported brick_dim");
