@@ -307,7 +307,8 @@ typedef struct vhx_dense_in {
  * meets become Parted bricks (rewritten in their slot, or given a new one), emptied bricks and nodes are unlinked up to
  * the root; new nodes, bricks and colours are appended after node_count, brick_count and color_count, a colour the
  * palette holds keeps its lowest index; solid_values and data_palette never change. Slots are not reused and nothing is
- * re-simplified (vhx_tree_orphans counts the unlinked slots; vhx_compact_tree drops them). The tree's
+ * re-simplified (vhx_tree_orphans counts the unlinked slots; vhx_compact_tree drops them, vhx_simplify_tree drops them and
+ * simplifies the tree again). The tree's
  * buffers grow as needed, contents kept, and vhx_tree_counts reports the new counts. on_device as
  * vhx_build_tree_dense. Ordered like vhx_update_ranges: owner context only (VHX_E_STATE on a shared one), frames
  * submitted before it see the old tree, frames after it the new one; returns when the tree is ready. A refused call
@@ -336,6 +337,33 @@ int vhx_tree_orphans(const vhx_ctx *ctx, uint32_t *nodes, uint32_t *bricks);
  * Node MIP descriptors computed before a compaction are invalid after it. A streamed view's host cache (vhx_stream.h)
  * keeps slot numbers of the device buffers: compacting under it invalidates them, so the caller must not do it. */
 int vhx_compact_tree(vhx_ctx *ctx, uint32_t *nodes_dropped, uint32_t *bricks_dropped);
+/* Simplifies the resident tree on the device, as BoxTree::simplify(ROOT, recursive) does on the host, and compacts it in
+ * the same pass: the image of vhx_flat_simplify (vhx_boxtree.h, which states the rules) of the tree, bit for bit in all
+ * seven buffers and counts, whenever both accept the tree. A Parted brick of one value becomes a Solid brick, or an
+ * empty entry where the value points to empty; a Leaf whose 64 bricks are the same Solid brick becomes a UniformLeaf
+ * over it, and (brick_dim > 1) a Leaf whose aligned 4x4x4 voxel blocks are each one value a UniformLeaf over one new
+ * Parted brick of the block values; an Internal node with occupied_bits 0 becomes Nothing and its subtree leaves.
+ * solid_values become the distinct values of the Solid entries that remain, in order of first (node, sectant); cells
+ * keep their words (data values included) and both palettes with their counts are untouched. After a series of
+ * vhx_write_dense calls the tree is the one vhx_build_tree_dense_simplified gives for the same voxels, up to the order
+ * of the palette. vhx_read_dense of any box is unchanged. vhx_get_voxels is unchanged except at a position whose stored
+ * value points to empty without being VHX_EMPTY, which may now read raw (under a UniformLeaf) or empty, as described
+ * for those node kinds above. Traces are those of the new image: a hit in a Solid brick reports the brick's cube, no
+ * cell, and an impact computed on that cube.
+ * Contract as vhx_compact_tree: out of place through new buffers at the new counts (peak device memory the old tree
+ * plus the new one), nothing of the old tree written, a refused call or a failed allocation leaves it bit for bit as it
+ * was; owner context only (VHX_E_STATE on a shared one); frames submitted before it trace the old buffers, frames after
+ * it the new ones; returns when the tree is ready; afterwards vhx_tree_orphans reports (0, 0) and the buffers hold what
+ * an upload of the new image would. VHX_E_STATE before any upload, while node MIPs are set, and for a malformed tree
+ * (vhx_compact_tree's cases, and a Solid entry whose index is at or past solid_count). VHX_E_CAPACITY, tree unchanged,
+ * where the new image would hold more than 65,535 distinct Solid values (they are ranked through the builders' colour
+ * table) or 2^31 bricks. *nodes_dropped / *bricks_dropped (either may be NULL) receive the old counts minus the new
+ * ones; *bricks_dropped is 0 where the new image holds more bricks than the old (Leaf nodes of Solid bricks that became
+ * UniformLeaf nodes over new Parted bricks). A vhx_sync after the call reports the device time of its classify pass
+ * (the one read of the old tree's cells) in place of a trace's.
+ * Node MIP descriptors computed before the call are invalid after it. A streamed view's host cache (vhx_stream.h)
+ * keeps slot numbers of the device buffers: simplifying under it invalidates them, so the caller must not do it. */
+int vhx_simplify_tree(vhx_ctx *ctx, uint32_t *nodes_dropped, uint32_t *bricks_dropped);
 
 /* Tracing --------------------------------------------------------------------------------------------------- */
 /* Traces primary rays for every pixel of the square tiles k = tile_start, tile_start+tile_stride, ... (raster order

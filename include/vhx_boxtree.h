@@ -27,6 +27,8 @@
  *   vhx_dense_build            <- the same for a caller's dense voxel grid (vhx_dense_desc, vhx.h)
  *   vhx_dense_build_simplified <- that tree after BoxTree::simplify(ROOT, recursive), as load_vox_file leaves a model
  *   vhx_flat_compact           <- no reference counterpart: an edited image without its orphaned slots, renumbered
+ *   vhx_flat_simplify          <- that image after BoxTree::simplify(ROOT, recursive), as insert / clear leave a tree
+ *                                 with auto-simplify on
  *
  * Tree type parameter: T = u32 (the reference default, BoxTree<T = u32>, src/boxtree/types.rs:219).
  */
@@ -165,6 +167,32 @@ int vhx_flat_desc(const vhx_flat *flat, vhx_tree_desc *desc);
  * index at or past node_count, a Parted index at or past brick_count, a node or Parted brick reached twice, or more
  * than 8 node levels. */
 int vhx_flat_compact(const vhx_tree_desc *tree, vhx_flat **out);
+/* The simplified image of `tree`: vhx_flat_compact, the host BoxTree of that image, vhx_boxtree_simplify(tree,
+ * recursive = 1) and vhx_boxtree_flatten in one call (no algorithm of its own); the CPU counterpart of
+ * vhx_simplify_tree (vhx.h), bit for bit. The result is a pure function of the image, with the reference's quirks kept:
+ *   points_to_empty(v): colour index v & 0xFFFF and data index v >> 16; the colour is none when the index is 0xFFFF, at
+ *     or past color_count, or names a colour of alpha 0; the data is none when the index is 0xFFFF, at or past
+ *     data_count, or names the value 0; v points to empty when both are none.
+ *   Reachability and numbering as vhx_flat_compact, except that an Internal node whose occupied_bits are 0 becomes
+ *     Nothing and its subtree leaves the image (tested top-down, before its children are looked at). Internal nodes
+ *     never collapse otherwise (the reference tests the parent's content there, which never holds). occupied_bits
+ *     move unchanged.
+ *   UniformLeaf: an empty entry 0 stays; Solid v: the node becomes Nothing if v points to empty; a Parted brick whose
+ *     cells all equal v: entry 0 becomes VHX_EMPTY if v points to empty, else Solid v; any other brick stays. Entries
+ *     1..63 are VHX_EMPTY.
+ *   Leaf, per entry: Solid v becomes empty if v points to empty; a Parted brick whose cells all equal v becomes empty
+ *     if v points to empty, else Solid v; other entries stay. Then, as a whole: (a) 64 Solid entries of one value: a
+ *     UniformLeaf over that Solid brick; (b) else, brick_dim 1: a Leaf of those entries; (c) else read the leaf as a
+ *     cube of 4 * brick_dim voxels an edge (an empty entry reads 0xFFFFFFFF, a Solid brick its value, a Parted brick
+ *     its cell): if every voxel of every aligned 4x4x4 block equals the block's corner voxel, a UniformLeaf over one
+ *     new Parted brick whose cell (x, y, z) is voxel (4x, 4y, 4z); otherwise a Leaf of those entries. A Leaf whose
+ *     entries all became empty falls into (c) and becomes a UniformLeaf over a brick of 0xFFFFFFFF cells, so the
+ *     function is not idempotent there.
+ *   solid_values: the distinct values of the result's Solid entries, each once, in order of first (new node,
+ *     sectant); unused old values leave. Both palettes and their counts are untouched; cells keep their words.
+ * Errors as vhx_flat_compact; VHX_E_TREE_INVALID_STRUCTURE also for a Solid entry at or past solid_count and where the
+ * host tree refuses the image (sizes vhx_boxtree_new refuses, a palette with duplicate or empty entries). */
+int vhx_flat_simplify(const vhx_tree_desc *tree, vhx_flat **out);
 void vhx_flat_free(vhx_flat *flat);
 
 /* MagicaVoxel .vox import — BoxTree::<u32>::load_vox_file(filename, brick_dimension) (src/convert/magicavoxel.rs:

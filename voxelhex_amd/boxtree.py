@@ -281,6 +281,13 @@ def _compacted(image):
     return FlatTree(h.value)
 
 
+def _simplified(image):
+    """vhx_flat_simplify of a FlatTree or TreeImage, as a new FlatTree."""
+    h = ctypes.c_void_p()
+    _tree_check(N.lib().vhx_flat_simplify(ctypes.byref(image.desc), ctypes.byref(h)), "simplified: a malformed image")
+    return FlatTree(h.value)
+
+
 class TreeImage:
     """A flattened tree held in numpy arrays (Raytracer.download): the seven arrays and counts of a vhx_tree_desc,
     under FlatTree's names; `desc` points into them, so the image uploads, traces on the oracle and saves like one."""
@@ -291,6 +298,15 @@ class TreeImage:
         device, bit for bit. Cells, solid values and palettes are unchanged. InvalidStructure for a malformed image (an
         index past its count, a node or brick reached twice, more than 8 levels)."""
         return _compacted(self)
+
+    def simplified(self):
+        """vhx_flat_simplify: compacted(), then the image BoxTree.simplify(recursive=True) leaves of it, as a FlatTree --
+        what Raytracer.simplify leaves on the device, bit for bit. Bricks of one value become Solid (or empty where the
+        value points to empty), leaves of one Solid brick or of homogeneous 4x4x4 blocks become UniformLeaf nodes, an
+        Internal node without occupied bits becomes Nothing; solid_values are renumbered by first use, cells keep their
+        words and the palettes stay (include/vhx_boxtree.h states every rule). InvalidStructure for a malformed image
+        and for one the host tree refuses (a palette with duplicate entries)."""
+        return _simplified(self)
 
     def __init__(self, boxtree_size, brick_dim, arrays):
         self.desc = N.TreeDesc()
@@ -364,6 +380,11 @@ class FlatTree:
     def compacted(self):
         """vhx_flat_compact (see TreeImage.compacted): a freshly built image comes back equal to itself."""
         return _compacted(self)
+
+    def simplified(self):
+        """vhx_flat_simplify (see TreeImage.simplified): from_dense(grid, ...).simplified() is
+        from_dense(grid, ..., simplify=True)."""
+        return _simplified(self)
 
     @classmethod
     def _from_handle(cls, h):

@@ -1,6 +1,7 @@
 // The pieces of the dense build (vhx_build.hip) that the in-place dense write (vhx_edit.hip) uses as well: the colour
 // table with its insert, lookup, compaction and ranking, the scans over occupancy words, and the counters read back.
-// The compaction (vhx_compact.hip) uses the scans.
+// The compaction (vhx_compact.hip) uses the scans; the simplification (vhx_simplify.hip) the scans and the table, for
+// the distinct Solid values.
 // Each unit that includes this gets its own copy of the kernels (anonymous namespace).
 #pragma once
 #include <hip/hip_runtime.h>

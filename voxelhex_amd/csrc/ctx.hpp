@@ -1,6 +1,6 @@
 // Internal context of libvhx, shared by the translation units of the device side: vhx_device.hip (tracing), vhx_tree.hip
 // (the device tree), vhx_ctx.hip (contexts, ordering, settings), vhx_mgpu.hip, vhx_build.hip, vhx_query.hip,
-// vhx_edit.hip and vhx_compact.hip.
+// vhx_edit.hip, vhx_compact.hip and vhx_simplify.hip.
 // Not part of the ABI: callers see vhx_ctx only as an opaque pointer (include/vhx.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -150,6 +150,14 @@ struct vhx_ctx {
     struct CompactScratch {
         DevBuf new_of, old_of, nmask, nrank, bmask, bfirst, bnew, bsrc, ctl;
     } compact;
+    // vhx_simplify_tree (vhx_simplify.hip): per new node its class with the bricks it contributes, the masks of its
+    // Parted entries after simplification and of the bricks it keeps, and its first new brick; per new child entry the
+    // Solid value or old brick it stands for; the source of every new brick; per new node the brick written anew for
+    // it; the counters read back. Reset by each call; the node maps are the compaction's, the table of the Solid
+    // values and the scans' block sums the build's
+    struct SimplifyScratch {
+        DevBuf binfo, pmask, gmask, bfirst, ent, bsrc, newb, ctl;
+    } simplify;
     // depth-prepass mode (vhx_set_depth_prepass; opt-in, not the reference path)
     bool prepass = false, in_prepass = false;
     // fused hard shadows (vhx_set_shadow_light): each hit's shadow ray traced in the lane that finished its primary ray
@@ -331,12 +339,17 @@ struct FreshTree {
 uint64_t raw_bytes(const vhx_tree_desc &counts, int id);
 // allocates fresh->hdr, brick_occ, child_rec (brick_dim <= 4) and the four node and voxel buffers at `counts`, and a
 // palette buffer where the tree's own is larger than an upload's; on failure frees what it allocated: the tree is untouched
-int alloc_fresh_tree(vhx_ctx *c, const vhx_tree_desc &counts, FreshTree *fresh);
+// new_solids (vhx_simplify_tree): a solid_values buffer for counts.solid_count in any case, which the caller fills
+int alloc_fresh_tree(vhx_ctx *c, const vhx_tree_desc &counts, FreshTree *fresh, bool new_solids = false);
 void free_fresh_tree(FreshTree *fresh);
 // makes `fresh` (raw buffers and bitmaps filled) the tree of c's store with the counts of `counts`: copies the kept
 // palettes, swaps the buffers in, derives headers and child records from them with finish_upload's kernels, waits for
 // c's stream (which inside a WriteScope already waits for the frames in flight) and frees the old buffers
-int adopt_fresh_tree(vhx_ctx *c, const vhx_tree_desc &counts, FreshTree *fresh);
+// new_solids: fresh's solid_values are the caller's and counts.solid_count becomes the tree's
+int adopt_fresh_tree(vhx_ctx *c, const vhx_tree_desc &counts, FreshTree *fresh, bool new_solids = false);
+// vhx_simplify_tree: the bitmaps of the bricks of `fresh` that were written anew instead of gathered, from their cells
+// and the tree's palettes, on c's stream. list[n] (device) names them by their new index; VHX_EMPTY entries are skipped
+int derive_fresh_occ(vhx_ctx *c, const vhx_tree_desc &counts, const FreshTree &fresh, const uint32_t *list, uint32_t n);
 // rebuilds DevTree::child_rec on c's stream when an update left it stale (every trace calls it before its first launch)
 int refresh_child_rec(vhx_ctx *c);
 // k_untile_planes on `stream` (arguments as vhx_untile_frame, already validated)

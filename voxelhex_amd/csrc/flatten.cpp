@@ -898,6 +898,35 @@ int vhx_flat_compact(const vhx_tree_desc *tree, vhx_flat **out) {
         return VHX_E_CAPACITY;
     }
 }
+int vhx_flat_simplify(const vhx_tree_desc *tree, vhx_flat **out) {
+    if (!out) return VHX_E_INVALID_ARG;
+    *out = nullptr;
+    if (!tree) return VHX_E_INVALID_ARG;
+    try {
+        vhx_flat *packed = nullptr;
+        int rc = compact_image(*tree, &packed);
+        if (rc != VHX_OK) return rc;
+        std::unique_ptr<vhx_flat> owned(packed);
+        // tree_of_flat reads solid_values by the entries' indices
+        for (size_t i = 0; i < packed->node_type.size(); ++i) {
+            const uint32_t ty = packed->node_type[i];
+            const uint32_t entries = ty == VHX_NODE_LEAF ? 64u : ty == VHX_NODE_UNIFORM_LEAF ? 1u : 0u;
+            for (uint32_t s = 0; s < entries; ++s) {
+                const uint32_t e = packed->node_children[i * 64 + s];
+                if (e != VHX_EMPTY && (e & VHX_SOLID_BIT) && (e & ~VHX_SOLID_BIT) >= packed->solid_values.size())
+                    return VHX_E_TREE_INVALID_STRUCTURE;
+            }
+        }
+        std::unique_ptr<BoxTree> t(tree_of_flat(*packed));
+        if (!t) return VHX_E_TREE_INVALID_STRUCTURE;
+        owned.reset();
+        t->simplify(0, true);
+        *out = flatten_tree(*t);
+        return VHX_OK;
+    } catch (const std::bad_alloc &) {
+        return VHX_E_CAPACITY;
+    }
+}
 void vhx_flat_free(vhx_flat *f) { delete f; }
 
 }  // extern "C"

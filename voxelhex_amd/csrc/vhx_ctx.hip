@@ -234,7 +234,9 @@ void vhx_destroy(vhx_ctx *c) {
                       &c->build.simp, &c->work, &c->query, &c->edit.oldn, &c->edit.aft, &c->edit.need,
                       &c->edit.rank, &c->edit.nmask, &c->edit.first, &c->edit.ctl, &c->compact.new_of,
                       &c->compact.old_of, &c->compact.nmask, &c->compact.nrank, &c->compact.bmask,
-                      &c->compact.bfirst, &c->compact.bnew, &c->compact.bsrc, &c->compact.ctl})
+                      &c->compact.bfirst, &c->compact.bnew, &c->compact.bsrc, &c->compact.ctl, &c->simplify.binfo,
+                      &c->simplify.pmask, &c->simplify.gmask, &c->simplify.bfirst, &c->simplify.ent,
+                      &c->simplify.bsrc, &c->simplify.newb, &c->simplify.ctl})
         if (b->ptr) (void)hipFree(b->ptr);
     if (c->tail_stream) {
         (void)hipStreamSynchronize(c->tail_stream);

@@ -2,12 +2,13 @@
 //
 // Kernels
 //   k_brick_occ_ballot / k_brick_occ_small  brick occupancy bitmaps from pix_points_to_empty (src/boxtree/node.rs:311-333)
+//   k_brick_occ_list  the same for the bricks a list names (vhx_simplify_tree's new bricks)
 //   k_pack_hdr        node type + occupied_bits -> one 16-byte record per node
 //   k_child_rec       DevTree::child_rec (brick_dim <= 4): one record per child entry
 //   k_scatter_ranges  ranged writes: staged pieces copied to their device addresses
 // Host side: upload (vhx_upload_tree*, receive_tree), ranged updates (vhx_update_range(s)), node MIPs, read-back of the
 // derived layout, content-preserving growth of the buffers for vhx_write_dense (grow_tree), the buffer swap of
-// vhx_compact_tree (alloc_fresh_tree, adopt_fresh_tree), vhx_tree_orphans. Launches no kernel of another unit; the trace unit (vhx_device.hip) calls refresh_child_rec.
+// vhx_compact_tree and vhx_simplify_tree (alloc_fresh_tree, derive_fresh_occ, adopt_fresh_tree), vhx_tree_orphans. Launches no kernel of another unit; the trace unit (vhx_device.hip) calls refresh_child_rec.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -47,6 +48,32 @@ __global__ void __launch_bounds__(256) k_brick_occ_small(const uint32_t *__restr
     for (uint32_t c = 0; c < n3; ++c)
         if (!cell_empty(vox[(uint64_t)b * n3 + c], color, ncolor, data, ndata)) m |= 1ull << c;
     words[b] = m;
+}
+
+// ... of the bricks a list names (the bricks a simplification wrote anew instead of gathering them with their bitmaps): a
+// wave per list entry, VHX_EMPTY entries skipped; bit order as the two kernels above
+__global__ void __launch_bounds__(256) k_brick_occ_list(const uint32_t *__restrict__ vox,
+                                                        const uint32_t *__restrict__ list, uint32_t n, uint32_t n3,
+                                                        const uint32_t *__restrict__ color, uint32_t ncolor,
+                                                        const uint32_t *__restrict__ data, uint32_t ndata,
+                                                        uint64_t *__restrict__ words) {
+    const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    if ((gid >> 6) >= n) return;  // the whole wave
+    const uint32_t b = list[gid >> 6];
+    if (b == VHX_EMPTY) return;
+    if (n3 < 64) {
+        const uint32_t v = vox[(uint64_t)b * n3 + (lane < n3 ? lane : 0u)];
+        const bool full = lane < n3 && !cell_empty(v, color, ncolor, data, ndata);
+        const uint64_t m = __ballot(full);
+        if (lane == 0) words[b] = m;
+        return;
+    }
+    const uint32_t nw = n3 >> 6;
+    for (uint32_t w = 0; w < nw; ++w) {
+        const uint64_t m = __ballot(!cell_empty(vox[(uint64_t)b * n3 + w * 64u + lane], color, ncolor, data, ndata));
+        if (lane == 0) words[(uint64_t)b * nw + w] = m;
+    }
 }
 
 // DevTree::child_rec for brick_dim <= 4: one record per child entry. Entries [e0, e1) are visited; with sel, only the
@@ -206,6 +233,19 @@ static int rebuild_occ(vhx_ctx *c, uint32_t brick0, uint32_t nbricks) {
     return VHX_OK;
 }
 
+int vhx::derive_fresh_occ(vhx_ctx *c, const vhx_tree_desc &counts, const FreshTree &fresh, const uint32_t *list,
+                          uint32_t n) {
+    if (counts.brick_count == 0 || n == 0) return VHX_OK;
+    const TreeStore &ts = *c->tree;
+    const uint32_t bd = ts.desc.brick_dim;
+    k_brick_occ_list<<<(unsigned)(((uint64_t)n * 64 + 255) / 256), 256, 0, c->stream>>>(
+        (const uint32_t *)fresh.raw[VHX_BUF_VOXELS].ptr, list, n, bd * bd * bd,
+        (const uint32_t *)ts.raw[VHX_BUF_COLOR_PALETTE].ptr, ts.desc.color_count,  // the palettes do not change
+        (const uint32_t *)ts.raw[VHX_BUF_DATA_PALETTE].ptr, ts.desc.data_count, (uint64_t *)fresh.brick_occ.ptr);
+    VHX_HIP(c, hipGetLastError());
+    return VHX_OK;
+}
+
 int vhx::alloc_tree(vhx_ctx *c, const vhx_tree_desc *t) {
     const uint32_t bd = t->brick_dim;
     if (t->node_count == 0 || bd == 0 || t->boxtree_size == 0 || (bd & (bd - 1)) != 0 || bd > 32 ||
@@ -301,7 +341,7 @@ void vhx::free_fresh_tree(FreshTree *f) {
     }
 }
 
-int vhx::alloc_fresh_tree(vhx_ctx *c, const vhx_tree_desc &counts, FreshTree *f) {
+int vhx::alloc_fresh_tree(vhx_ctx *c, const vhx_tree_desc &counts, FreshTree *f, bool new_solids) {
     const TreeStore &ts = *c->tree;
     struct Want {
         DevBuf *b;
@@ -310,7 +350,8 @@ int vhx::alloc_fresh_tree(vhx_ctx *c, const vhx_tree_desc &counts, FreshTree *f)
     uint32_t n = 0;
     for (int id = 0; id < 7; ++id) {
         const bool palette = id >= VHX_BUF_SOLID_VALUES;
-        if (palette && ts.raw[id].bytes <= raw_bytes(counts, id)) continue;  // kept as it is
+        const bool fresh = new_solids && id == VHX_BUF_SOLID_VALUES;
+        if (palette && !fresh && ts.raw[id].bytes <= raw_bytes(counts, id)) continue;  // kept as it is
         want[n++] = {&f->raw[id], raw_bytes(counts, id)};
     }
     const uint64_t occ_bytes = (uint64_t)counts.brick_count * ts.occ_words * 8;
@@ -323,18 +364,19 @@ int vhx::alloc_fresh_tree(vhx_ctx *c, const vhx_tree_desc &counts, FreshTree *f)
             want[i].b->ptr = nullptr;
             free_fresh_tree(f);
             (void)hipGetLastError();
-            return fail(c, VHX_E_HIP, std::string("vhx_compact_tree: hipMalloc: ") + hipGetErrorString(e));
+            return fail(c, VHX_E_HIP,
+                        std::string("vhx_compact_tree / vhx_simplify_tree: hipMalloc: ") + hipGetErrorString(e));
         }
         want[i].b->bytes = want[i].bytes;
     }
     return VHX_OK;
 }
 
-int vhx::adopt_fresh_tree(vhx_ctx *c, const vhx_tree_desc &counts, FreshTree *f) {
+int vhx::adopt_fresh_tree(vhx_ctx *c, const vhx_tree_desc &counts, FreshTree *f, bool new_solids) {
     TreeStore &ts = *c->tree;
     for (int id = VHX_BUF_SOLID_VALUES; id < 7; ++id) {
         const uint64_t used = elem_count(counts, id) * elem_size(id);
-        if (f->raw[id].ptr && used)
+        if (f->raw[id].ptr && used && !(new_solids && id == VHX_BUF_SOLID_VALUES))
             VHX_HIP(c, hipMemcpyAsync(f->raw[id].ptr, ts.raw[id].ptr, used, hipMemcpyDeviceToDevice, c->stream));
     }
     for (int id = 0; id < 7; ++id)
@@ -344,6 +386,7 @@ int vhx::adopt_fresh_tree(vhx_ctx *c, const vhx_tree_desc &counts, FreshTree *f)
     if (has_child_rec(c)) std::swap(ts.child_rec, f->child_rec);
     ts.desc.node_count = counts.node_count;
     ts.desc.brick_count = counts.brick_count;
+    if (new_solids) ts.desc.solid_count = counts.solid_count;
     ts.orphan_nodes = ts.orphan_bricks = 0;
     int rc = rebuild_hdr(c, 0, counts.node_count);
     if (!rc && has_child_rec(c)) {

@@ -413,6 +413,24 @@ class Raytracer:
             self._tree = _BuiltOnDevice()  # no longer the uploaded FlatTree: upload() of it must upload again
         return n.value, b.value
 
+    def simplify(self):
+        """vhx_simplify_tree: simplifies the resident tree on the device as BoxTree.simplify(recursive=True) does on the
+        host, and compacts it in the same pass (download() then equals download().simplified() of before, bit for bit):
+        bricks of one value become Solid or empty, leaves of one Solid brick or of homogeneous 4x4x4 blocks become
+        UniformLeaf nodes, orphans leave, solid_values are renumbered by first use; cells keep their data values and the
+        palettes stay. After write_dense / fill_box edits it leaves the tree build_dense(simplify=True) gives for the same
+        voxels. read_dense is unchanged; traces are those of the new image. Returns (nodes_dropped, bricks_dropped), the
+        old counts minus the new. Contract as compact(): out of place, owner context only, not while node MIPs are set,
+        not under a streamed view; a refused call leaves the tree as it was. VHX_E_CAPACITY (tree unchanged) past 65,535
+        distinct Solid values. Against read_dense + build_dense(simplify=True), the only other way back to a simplified
+        tree, it needs no dense grid on the host or device, keeps data values and palette order and shrinks the buffers;
+        DESIGN.md §8.9 says how the two compare in time."""
+        n, b = ctypes.c_uint32(), ctypes.c_uint32()
+        self._check(N.lib().vhx_simplify_tree(self._h, ctypes.byref(n), ctypes.byref(b)))
+        if not isinstance(self._tree, _BuiltOnDevice):
+            self._tree = _BuiltOnDevice()  # no longer the uploaded FlatTree: upload() of it must upload again
+        return n.value, b.value
+
     def update_range(self, buffer_id, elem_offset, values):
         values = np.ascontiguousarray(values)
         self._check(N.lib().vhx_update_range(self._h, buffer_id, elem_offset, values.size, values.ctypes.data))
