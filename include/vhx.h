@@ -346,7 +346,8 @@ int vhx_compact_tree(vhx_ctx *ctx, uint32_t *nodes_dropped, uint32_t *bricks_dro
  * solid_values become the distinct values of the Solid entries that remain, in order of first (node, sectant); cells
  * keep their words (data values included) and both palettes with their counts are untouched. After a series of
  * vhx_write_dense calls the tree is the one vhx_build_tree_dense_simplified gives for the same voxels, up to the order
- * of the palette. vhx_read_dense of any box is unchanged. vhx_get_voxels is unchanged except at a position whose stored
+ * of the palette; vhx_compact_palette after it closes that caveat (the image is then the build's, bit for bit).
+ * vhx_read_dense of any box is unchanged. vhx_get_voxels is unchanged except at a position whose stored
  * value points to empty without being VHX_EMPTY, which may now read raw (under a UniformLeaf) or empty, as described
  * for those node kinds above. Traces are those of the new image: a hit in a Solid brick reports the brick's cube, no
  * cell, and an impact computed on that cube.
@@ -364,6 +365,29 @@ int vhx_compact_tree(vhx_ctx *ctx, uint32_t *nodes_dropped, uint32_t *bricks_dro
  * Node MIP descriptors computed before the call are invalid after it. A streamed view's host cache (vhx_stream.h)
  * keeps slot numbers of the device buffers: simplifying under it invalidates them, so the caller must not do it. */
 int vhx_simplify_tree(vhx_ctx *ctx, uint32_t *nodes_dropped, uint32_t *bricks_dropped);
+/* Rewrites the colour half of the resident tree on the device, in place, so that color_palette is the builders' palette
+ * of the voxels the tree holds now: the image of vhx_flat_compact_palette (vhx_boxtree.h, which states the rules) of the
+ * tree, bit for bit. Colours no reachable value names leave the palette, entries holding the same colour become one,
+ * and the colours that stay are ordered by the first index of the cubes that hold them, (x * boxtree_size + y) *
+ * boxtree_size + z of a cube's min corner -- the order of the builders' insert loop. Every cell of every brick slot
+ * (orphaned ones included) and every entry of solid_values becomes (v & 0xFFFF0000) | map[v & 0xFFFF]; map is 0xFFFF
+ * for an index that named no colour. Data halves, data_palette, node types, occupancy, entries, the counts of nodes,
+ * bricks and solids and the order of solid_values are untouched; color_count becomes the number of used colours
+ * (vhx_tree_counts) and *colors_dropped (may be NULL) receives the old count minus the new. Buffers are not
+ * reallocated (vhx_tree_device_bytes is unchanged). vhx_read_dense of any box and every trace field but `value` are
+ * unchanged; `value`, from a trace or vhx_get_voxels, is the old one through the map. So after vhx_write_dense calls,
+ * vhx_simplify_tree and this call leave exactly the image vhx_build_tree_dense_simplified gives for the same voxels,
+ * vhx_compact_tree and this call the image of vhx_build_tree_dense, and a palette that an editing session has filled
+ * with colours no voxel holds any more (VHX_E_CAPACITY from vhx_write_dense) has room again.
+ * The tree is only read until the one readback of the counters, so a refused call leaves it bit for bit as it was:
+ * VHX_E_STATE before any upload, on a shared context, while node MIPs are set (MIP bricks are not reachable through
+ * the entries, their colours would be dropped), and for a malformed tree (vhx_compact_tree's cases, a Solid entry at
+ * or past solid_count, a Leaf or UniformLeaf so deep that a cell of its bricks is smaller than a voxel). Ordered like
+ * vhx_write_dense: owner context only, the call waits for the frames in flight on every context of the tree, frames
+ * submitted after it see the new tree; returns when the tree is ready. A vhx_sync after the call reports the device
+ * time of its rewrite pass (the one read and write of the voxel buffer) in place of a trace's.
+ * A streamed view's host cache (vhx_stream.h) keeps palette indices: the caller must not call this under it. */
+int vhx_compact_palette(vhx_ctx *ctx, uint32_t *colors_dropped);
 
 /* Tracing --------------------------------------------------------------------------------------------------- */
 /* Traces primary rays for every pixel of the square tiles k = tile_start, tile_start+tile_stride, ... (raster order

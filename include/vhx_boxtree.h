@@ -29,6 +29,7 @@
  *   vhx_flat_compact           <- no reference counterpart: an edited image without its orphaned slots, renumbered
  *   vhx_flat_simplify          <- that image after BoxTree::simplify(ROOT, recursive), as insert / clear leave a tree
  *                                 with auto-simplify on
+ *   vhx_flat_compact_palette   <- no reference counterpart: an edited image with the colour palette of a fresh build
  *
  * Tree type parameter: T = u32 (the reference default, BoxTree<T = u32>, src/boxtree/types.rs:219).
  */
@@ -193,6 +194,34 @@ int vhx_flat_compact(const vhx_tree_desc *tree, vhx_flat **out);
  * Errors as vhx_flat_compact; VHX_E_TREE_INVALID_STRUCTURE also for a Solid entry at or past solid_count and where the
  * host tree refuses the image (sizes vhx_boxtree_new refuses, a palette with duplicate or empty entries). */
 int vhx_flat_simplify(const vhx_tree_desc *tree, vhx_flat **out);
+/* The image `tree` with a canonical colour palette: color_palette becomes the palette the builders (vhx_dense_build)
+ * give the voxels the image holds now, and every cell and solid value is translated to it; the CPU counterpart of
+ * vhx_compact_palette (vhx.h), bit for bit. Nothing is renumbered or dropped but colours: counts of nodes, bricks and
+ * solids, the order of solid_values, node types, occupancy, entries, data halves and data_palette stay.
+ *   Reachability: nodes and Parted bricks are reachable as for vhx_flat_compact. A reachable value is every cell of a
+ *     reachable Parted brick and the solid_values entry of every Solid entry of a reachable Leaf (its 64 entries) or
+ *     UniformLeaf (entry 0).
+ *   A value v names a colour when ci = v & 0xFFFF is not 0xFFFF, ci < color_count and the alpha byte of
+ *     color_palette[ci] is not 0 (the colour half of points_to_empty, above). A colour is used when a reachable value
+ *     names it; palette entries holding the same 32-bit colour are one colour.
+ *   Every reachable value sits on an axis-aligned cube: a cell of a Leaf's Parted brick, the whole brick of a Leaf's
+ *     Solid entry, a cell of a UniformLeaf's brick, or the whole node where that brick is Solid. A node at level l
+ *     (the root is level 0) has the edge boxtree_size / 4^l and a Leaf's brick a quarter of it; a UniformLeaf's brick
+ *     spans the node; a cell is a brick_dim-th of its brick. The first index of a cube with min corner (x, y, z) is
+ *     (x * boxtree_size + y) * boxtree_size + z -- the position of that voxel in the builders' insert loop (x outer,
+ *     then y, z inner), which meets the min corner of a cube of one value before the rest of it. The first index of
+ *     a colour is the smallest one among the reachable values that name it.
+ *   The new color_palette holds the used colours in increasing first index; color_count is their number.
+ *   map[ci] is the new index of the colour of entry ci, and 0xFFFF where the entry is unused or of alpha 0 and for
+ *     every ci that names no colour. Every cell of every brick slot [0, brick_count), orphaned ones included (they keep
+ *     no colour alive), and every entry of solid_values becomes (v & 0xFFFF0000) | map[v & 0xFFFF]. So vhx_read_dense
+ *     and emptiness are unchanged, and a value whose colour half named nothing carries 0xFFFF there afterwards.
+ * The image of a dense build, plain or simplified, is returned as it is, and the function is idempotent.
+ * Errors as vhx_flat_simplify: VHX_E_INVALID_ARG for null arrays or a count of 0 nodes; VHX_E_TREE_INVALID_STRUCTURE,
+ * and no image, for vhx_flat_compact's cases, a reachable Solid entry at or past solid_count, and a reachable Leaf or
+ * UniformLeaf so deep that a cell of its bricks would be smaller than a voxel (its cubes would have no corner of their
+ * own). Duplicate palette entries are accepted. Node MIPs are not carried over. */
+int vhx_flat_compact_palette(const vhx_tree_desc *tree, vhx_flat **out);
 void vhx_flat_free(vhx_flat *flat);
 
 /* MagicaVoxel .vox import — BoxTree::<u32>::load_vox_file(filename, brick_dimension) (src/convert/magicavoxel.rs:

@@ -133,6 +133,7 @@ SIGNATURES = [
     ("vhx_tree_orphans", c_int, [c_void_p, P(c_u32), P(c_u32)]),
     ("vhx_compact_tree", c_int, [c_void_p, P(c_u32), P(c_u32)]),
     ("vhx_simplify_tree", c_int, [c_void_p, P(c_u32), P(c_u32)]),
+    ("vhx_compact_palette", c_int, [c_void_p, P(c_u32)]),
     ("vhx_set_node_mips", c_int, [c_void_p, c_void_p, c_u32]),
     ("vhx_update_range", c_int, [c_void_p, c_int, c_u64, c_u64, c_void_p]),
     ("vhx_update_ranges", c_int, [c_void_p, c_void_p, c_u32]),
@@ -208,6 +209,7 @@ SIGNATURES = [
     ("vhx_flat_desc", c_int, [c_void_p, P(TreeDesc)]),
     ("vhx_flat_compact", c_int, [P(TreeDesc), P(c_void_p)]),
     ("vhx_flat_simplify", c_int, [P(TreeDesc), P(c_void_p)]),
+    ("vhx_flat_compact_palette", c_int, [P(TreeDesc), P(c_void_p)]),
     ("vhx_boxtree_switch_mips", c_int, [c_void_p, c_int]),
     ("vhx_boxtree_set_mip_method", c_int, [c_void_p, c_u32, c_u32, c_f32]),
     ("vhx_boxtree_set_mip_color_threshold", c_int, [c_void_p, c_u32, c_f32]),

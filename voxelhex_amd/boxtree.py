@@ -288,9 +288,25 @@ def _simplified(image):
     return FlatTree(h.value)
 
 
+def _palette_compacted(image):
+    """vhx_flat_compact_palette of a FlatTree or TreeImage, as a new FlatTree."""
+    h = ctypes.c_void_p()
+    _tree_check(N.lib().vhx_flat_compact_palette(ctypes.byref(image.desc), ctypes.byref(h)),
+                "palette_compacted: a malformed image")
+    return FlatTree(h.value)
+
+
 class TreeImage:
     """A flattened tree held in numpy arrays (Raytracer.download): the seven arrays and counts of a vhx_tree_desc,
     under FlatTree's names; `desc` points into them, so the image uploads, traces on the oracle and saves like one."""
+
+    def palette_compacted(self):
+        """vhx_flat_compact_palette: this image with the colour palette the builders give the voxels it holds now, as a
+        FlatTree -- what Raytracer.compact_palette leaves on the device, bit for bit. Colours no reachable value names
+        leave, entries of one colour merge, the rest is ordered by first appearance in the builders' insert loop (x
+        outer, y, z inner); the colour half of every cell (orphaned slots included) and solid value is translated, and
+        nothing else changes (include/vhx_boxtree.h states every rule). InvalidStructure for a malformed image."""
+        return _palette_compacted(self)
 
     def compacted(self):
         """vhx_flat_compact: this image without its unreachable node and brick slots, renumbered as the builders number
@@ -385,6 +401,11 @@ class FlatTree:
         """vhx_flat_simplify (see TreeImage.simplified): from_dense(grid, ...).simplified() is
         from_dense(grid, ..., simplify=True)."""
         return _simplified(self)
+
+    def palette_compacted(self):
+        """vhx_flat_compact_palette (see TreeImage.palette_compacted): a freshly built image, plain or simplified, comes
+        back equal to itself."""
+        return _palette_compacted(self)
 
     @classmethod
     def _from_handle(cls, h):

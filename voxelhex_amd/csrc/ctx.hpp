@@ -1,6 +1,6 @@
 // Internal context of libvhx, shared by the translation units of the device side: vhx_device.hip (tracing), vhx_tree.hip
 // (the device tree), vhx_ctx.hip (contexts, ordering, settings), vhx_mgpu.hip, vhx_build.hip, vhx_query.hip,
-// vhx_edit.hip, vhx_compact.hip and vhx_simplify.hip.
+// vhx_edit.hip, vhx_compact.hip, vhx_simplify.hip and vhx_palette.hip.
 // Not part of the ABI: callers see vhx_ctx only as an opaque pointer (include/vhx.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -158,6 +158,12 @@ struct vhx_ctx {
     struct SimplifyScratch {
         DevBuf binfo, pmask, gmask, bfirst, ent, bsrc, newb, ctl;
     } simplify;
+    // vhx_compact_palette (vhx_palette.hip): per new node its origin and level, per palette index the smallest first
+    // index of a reachable value that names it and its new index, and the counters read back. Reset by each call; the
+    // node maps are the compaction's, the colour table and the scans' block sums the build's
+    struct PaletteScratch {
+        DevBuf org, first, map, ctl;
+    } palette;
     // depth-prepass mode (vhx_set_depth_prepass; opt-in, not the reference path)
     bool prepass = false, in_prepass = false;
     // fused hard shadows (vhx_set_shadow_light): each hit's shadow ray traced in the lane that finished its primary ray
@@ -350,6 +356,9 @@ int adopt_fresh_tree(vhx_ctx *c, const vhx_tree_desc &counts, FreshTree *fresh, 
 // vhx_simplify_tree: the bitmaps of the bricks of `fresh` that were written anew instead of gathered, from their cells
 // and the tree's palettes, on c's stream. list[n] (device) names them by their new index; VHX_EMPTY entries are skipped
 int derive_fresh_occ(vhx_ctx *c, const vhx_tree_desc &counts, const FreshTree &fresh, const uint32_t *list, uint32_t n);
+// vhx_compact_palette: the bitmaps of every brick slot from the cells, and the child records from them, on c's stream (a
+// cell of an orphaned slot may have named a colour that left the palette, and is empty now)
+int rederive_bricks(vhx_ctx *c);
 // rebuilds DevTree::child_rec on c's stream when an update left it stale (every trace calls it before its first launch)
 int refresh_child_rec(vhx_ctx *c);
 // k_untile_planes on `stream` (arguments as vhx_untile_frame, already validated)

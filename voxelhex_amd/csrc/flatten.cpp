@@ -630,6 +630,110 @@ static int compact_image(const vhx_tree_desc &t, vhx_flat **out) {
     return VHX_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- palette
+// The image with the colour palette the builders give the voxels it holds now (include/vhx_boxtree.h
+// states the rules): the used colours by the first index of the cubes that hold them, every cell and solid value
+// translated, nothing else touched. The CPU reference of vhx_compact_palette.
+static int palette_image(const vhx_tree_desc &t, vhx_flat **out) {
+    const uint32_t nn = t.node_count, nb = t.brick_count, bd = t.brick_dim;
+    const uint64_t n3 = (uint64_t)bd * bd * bd, S = t.boxtree_size;
+    if (nn == 0 || n3 == 0 || !t.node_type || !t.node_ocbits || !t.node_children || (nb && !t.voxels) ||
+        (t.solid_count && !t.solid_values) || (t.color_count && !t.color_palette) || (t.data_count && !t.data_palette))
+        return VHX_E_INVALID_ARG;
+    const uint32_t ncol = std::min<uint32_t>(t.color_count, 0xFFFFu);  // what a 16-bit index can name
+    std::vector<uint64_t> first(0x10000, ~0ull);  // per palette entry: the smallest first index of a value naming it
+    auto see = [&](uint32_t v, uint64_t x, uint64_t y, uint64_t z) {
+        const uint32_t ci = v & 0xFFFFu;
+        if (ci == 0xFFFFu) return;
+        first[ci] = std::min(first[ci], (x * S + y) * S + z);
+    };
+    struct At {
+        uint32_t node, level;
+        uint64_t x, y, z;
+    };
+    std::vector<At> order{{0, 0, 0, 0, 0}};
+    std::vector<uint8_t> seen_node(nn, 0), seen_brick(nb, 0);
+    seen_node[0] = 1;
+    for (size_t i = 0; i < order.size(); ++i) {
+        const At a = order[i];
+        if (a.level >= COMPACT_MAX_LEVELS) return VHX_E_TREE_INVALID_STRUCTURE;
+        const uint32_t ty = t.node_type[a.node];
+        const uint64_t size = S >> (2 * a.level), quarter = size >> 2;
+        const uint32_t *ent = t.node_children + (size_t)a.node * 64;
+        if (ty == VHX_NODE_INTERNAL) {
+            for (uint32_t s = 0; s < 64; ++s) {
+                const uint32_t e = ent[s];
+                if (e == VHX_EMPTY) continue;
+                if (e >= nn || seen_node[e]) return VHX_E_TREE_INVALID_STRUCTURE;  // past the count, or twice
+                seen_node[e] = 1;
+                order.push_back({e, a.level + 1, a.x + (s & 3u) * quarter, a.y + ((s >> 2) & 3u) * quarter,
+                                 a.z + (s >> 4) * quarter});
+            }
+            continue;
+        }
+        const bool uniform = ty == VHX_NODE_UNIFORM_LEAF;
+        if (!uniform && ty != VHX_NODE_LEAF) continue;
+        const uint64_t edge = uniform ? size : quarter, cell = edge / bd;  // of a brick, of one of its cells
+        if (cell == 0) return VHX_E_TREE_INVALID_STRUCTURE;  // a brick below the voxel lattice
+        for (uint32_t s = 0; s < (uniform ? 1u : 64u); ++s) {
+            const uint32_t e = ent[s];
+            if (e == VHX_EMPTY) continue;
+            const uint64_t bx = a.x + (s & 3u) * edge, by = a.y + ((s >> 2) & 3u) * edge, bz = a.z + (s >> 4) * edge;
+            if (e & VHX_SOLID_BIT) {
+                if ((e & ~VHX_SOLID_BIT) >= t.solid_count) return VHX_E_TREE_INVALID_STRUCTURE;
+                see(t.solid_values[e & ~VHX_SOLID_BIT], bx, by, bz);
+                continue;
+            }
+            if (e >= nb || seen_brick[e]) return VHX_E_TREE_INVALID_STRUCTURE;
+            seen_brick[e] = 1;
+            const uint32_t *cells = t.voxels + (size_t)e * n3;
+            for (uint32_t cz = 0, c = 0; cz < bd; ++cz)
+                for (uint32_t cy = 0; cy < bd; ++cy)
+                    for (uint32_t cx = 0; cx < bd; ++cx, ++c) see(cells[c], bx + cx * cell, by + cy * cell, bz + cz * cell);
+        }
+    }
+    // entries of one colour are one colour; an entry of alpha 0 names none
+    std::unordered_map<uint32_t, uint64_t> colour_first;
+    for (uint32_t ci = 0; ci < ncol; ++ci) {
+        const uint32_t col = t.color_palette[ci];
+        if (first[ci] == ~0ull || (col >> 24) == 0) continue;
+        auto it = colour_first.emplace(col, first[ci]).first;
+        it->second = std::min(it->second, first[ci]);
+    }
+    std::vector<std::pair<uint64_t, uint32_t>> ranked;
+    ranked.reserve(colour_first.size());
+    for (const auto &kv : colour_first) ranked.emplace_back(kv.second, kv.first);
+    std::sort(ranked.begin(), ranked.end());
+    std::unordered_map<uint32_t, uint32_t> index_of;
+    for (size_t r = 0; r < ranked.size(); ++r) index_of[ranked[r].second] = (uint32_t)r;
+    std::vector<uint32_t> map(0x10000, 0xFFFFu);
+    for (uint32_t ci = 0; ci < ncol; ++ci) {
+        const uint32_t col = t.color_palette[ci];
+        if ((col >> 24) == 0) continue;
+        const auto it = index_of.find(col);
+        if (it != index_of.end()) map[ci] = it->second;
+    }
+    auto mapped = [&](uint32_t v) { return (v & 0xFFFF0000u) | map[v & 0xFFFFu]; };
+
+    std::unique_ptr<vhx_flat> f(new vhx_flat());
+    f->size = t.boxtree_size;
+    f->brick_dim = bd;
+    f->node_type.assign(t.node_type, t.node_type + nn);
+    f->node_ocbits.assign(t.node_ocbits, t.node_ocbits + nn);
+    f->node_children.assign(t.node_children, t.node_children + (size_t)nn * 64);
+    f->brick_count = nb;
+    f->voxel_count = (uint64_t)nb * n3;
+    f->voxels.reset(new uint32_t[std::max<uint64_t>(f->voxel_count, 1)]);
+    for (uint64_t i = 0; i < f->voxel_count; ++i) f->voxels[i] = mapped(t.voxels[i]);  // orphaned slots included
+    f->solid_values.resize(t.solid_count);
+    for (uint32_t i = 0; i < t.solid_count; ++i) f->solid_values[i] = mapped(t.solid_values[i]);
+    f->color_palette.resize(ranked.size());
+    for (size_t r = 0; r < ranked.size(); ++r) f->color_palette[r] = ranked[r].second;
+    f->data_palette.assign(t.data_palette, t.data_palette + t.data_count);
+    *out = f.release();
+    return VHX_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- C ABI
 extern "C" {
 
@@ -894,6 +998,16 @@ int vhx_flat_compact(const vhx_tree_desc *tree, vhx_flat **out) {
     if (!tree) return VHX_E_INVALID_ARG;
     try {
         return compact_image(*tree, out);
+    } catch (const std::bad_alloc &) {
+        return VHX_E_CAPACITY;
+    }
+}
+int vhx_flat_compact_palette(const vhx_tree_desc *tree, vhx_flat **out) {
+    if (!out) return VHX_E_INVALID_ARG;
+    *out = nullptr;
+    if (!tree) return VHX_E_INVALID_ARG;
+    try {
+        return palette_image(*tree, out);
     } catch (const std::bad_alloc &) {
         return VHX_E_CAPACITY;
     }

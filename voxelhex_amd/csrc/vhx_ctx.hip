@@ -236,7 +236,8 @@ void vhx_destroy(vhx_ctx *c) {
                       &c->compact.old_of, &c->compact.nmask, &c->compact.nrank, &c->compact.bmask,
                       &c->compact.bfirst, &c->compact.bnew, &c->compact.bsrc, &c->compact.ctl, &c->simplify.binfo,
                       &c->simplify.pmask, &c->simplify.gmask, &c->simplify.bfirst, &c->simplify.ent,
-                      &c->simplify.bsrc, &c->simplify.newb, &c->simplify.ctl})
+                      &c->simplify.bsrc, &c->simplify.newb, &c->simplify.ctl, &c->palette.org, &c->palette.first,
+                      &c->palette.map, &c->palette.ctl})
         if (b->ptr) (void)hipFree(b->ptr);
     if (c->tail_stream) {
         (void)hipStreamSynchronize(c->tail_stream);

@@ -233,6 +233,13 @@ static int rebuild_occ(vhx_ctx *c, uint32_t brick0, uint32_t nbricks) {
     return VHX_OK;
 }
 
+int vhx::rederive_bricks(vhx_ctx *c) {
+    int rc = rebuild_occ(c, 0, c->tree->desc.brick_count);
+    if (rc || !has_child_rec(c)) return rc;
+    c->tree->child_rec_stale = true;
+    return refresh_child_rec(c);
+}
+
 int vhx::derive_fresh_occ(vhx_ctx *c, const vhx_tree_desc &counts, const FreshTree &fresh, const uint32_t *list,
                           uint32_t n) {
     if (counts.brick_count == 0 || n == 0) return VHX_OK;

@@ -424,12 +424,30 @@ class Raytracer:
         not under a streamed view; a refused call leaves the tree as it was. VHX_E_CAPACITY (tree unchanged) past 65,535
         distinct Solid values. Against read_dense + build_dense(simplify=True), the only other way back to a simplified
         tree, it needs no dense grid on the host or device, keeps data values and palette order and shrinks the buffers;
-        DESIGN.md §8.9 says how the two compare in time."""
+        DESIGN.md §8.9 says how the two compare in time. The palette keeps its dead colours and its edit order, so the
+        image is the build's only up to the order of the palette; compact_palette() after it closes that caveat."""
         n, b = ctypes.c_uint32(), ctypes.c_uint32()
         self._check(N.lib().vhx_simplify_tree(self._h, ctypes.byref(n), ctypes.byref(b)))
         if not isinstance(self._tree, _BuiltOnDevice):
             self._tree = _BuiltOnDevice()  # no longer the uploaded FlatTree: upload() of it must upload again
         return n.value, b.value
+
+    def compact_palette(self):
+        """vhx_compact_palette: rewrites the colour half of the resident tree on the device, in place, so that
+        color_palette is the builders' palette of the voxels the tree holds now (download() then equals
+        download().palette_compacted() of before, bit for bit): colours no reachable voxel names leave, entries of one
+        colour merge, the rest is in first-appearance order of the builders' insert loop, and every cell and solid value
+        is translated. After edits, simplify() then compact_palette() leaves exactly the image build_dense(simplify=True)
+        gives for the same voxels, compact() then compact_palette() that of a plain build_dense; and a palette filled up
+        by a long editing session (VHX_E_CAPACITY from write_dense) has room again. read_dense and every trace field but
+        `value` are unchanged; `value` (trace, get) is the old one with its colour index translated. Returns the colours
+        dropped. Buffers are not reallocated. Owner context only, not while node MIPs are set, not under a streamed view
+        (its host cache keeps palette indices); a refused call leaves the tree as it was. DESIGN.md §8.10."""
+        n = ctypes.c_uint32()
+        self._check(N.lib().vhx_compact_palette(self._h, ctypes.byref(n)))
+        if not isinstance(self._tree, _BuiltOnDevice):
+            self._tree = _BuiltOnDevice()  # no longer the uploaded FlatTree: upload() of it must upload again
+        return n.value
 
     def update_range(self, buffer_id, elem_offset, values):
         values = np.ascontiguousarray(values)
