@@ -393,7 +393,11 @@ int vhx_compact_palette(vhx_ctx *ctx, uint32_t *colors_dropped);
 /* Traces primary rays for every pixel of the square tiles k = tile_start, tile_start+tile_stride, ... (raster order
  * of ceil(W/T) x ceil(H/T) tiles, T = tile_size). tile_size 0 with layout FRAMEBUFFER traces the whole frame.
  * In the TILES layout, entries of pixels past the frame edge are not written (device outputs) or read back as 0
- * (host outputs). */
+ * (host outputs). In the FRAMEBUFFER layout with tile_start > 0 or tile_stride > 1 (a rank's share of a frame that
+ * several calls fill) the pixels of other tiles are not written. A shadow light (vhx_set_shadow_light) changes none
+ * of this: tile padding and other tiles' pixels are treated as without one, in `shadowed` and `rgba` too, on every
+ * schedule. With a light and device outputs, `shadowed` and `rgba` must not overlap `value`, `impact`, `normal` or each
+ * other: VHX_E_INVALID_ARG before anything is launched or written (host outputs are staged and cannot overlap). */
 int vhx_trace_primary(vhx_ctx *ctx, const vhx_camera *cam, uint32_t tile_size, uint32_t tile_start,
                       uint32_t tile_stride, uint32_t layout, const vhx_hits *out, int on_device);
 /* A batch of n whole frames (framebuffer layout, device outputs) traced as ONE pass ladder on the context's stream: pass
@@ -435,7 +439,14 @@ int vhx_set_depth_prepass(vhx_ctx *ctx, int enable, float margin);
  * while the nodes of its descent are still in that CU's caches; otherwise (a lone frame's schedule) the frame's shadow
  * rays are traced after its primary rays, as vhx_trace_shadows does. Results equal vhx_trace_primary followed by
  * vhx_trace_shadows bit for bit. light = NULL turns it off (the default). No byte counting, depth prepass or node
- * MIPs with a light set. */
+ * MIPs with a light set.
+ * A trace with a light writes `shadowed` (0 at primary misses) and darkens `rgba` only at the entries it owns: tile
+ * padding (TILES layout) and the pixels of other calls' tiles (a rank-sharded FRAMEBUFFER) are treated as without a
+ * light -- not written with device outputs, padding read back as 0 with host outputs -- whether the shadows are fused
+ * or traced after the primary rays; shard calls that fill one set of buffers one after another darken every pixel once.
+ * With device outputs, `shadowed` and `rgba` must not overlap the hit records (`value`, `impact`, `normal`) or each
+ * other, and in a batch no `shadowed` array may overlap any output array of any frame: VHX_E_INVALID_ARG, before
+ * anything is launched, on every schedule. */
 int vhx_set_shadow_light(vhx_ctx *ctx, const float *light);
 /* MIP stand-ins for absent children (the WGSL path's probe_MIP, src/raytracing/bevy/viewport_render.wgsl:328-364,
  * 438-454, enabled by tree_properties bit 16, streaming/mod.rs:288-290): node_mips[i] is node i's MIP brick descriptor

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import voxelhex_amd as vhx
+from tests._tilemask import tile_mask
 from voxelhex_amd import _native as N
 
 pytestmark = pytest.mark.gpu
@@ -84,7 +85,7 @@ def test_fused_frame_equals_primary_then_shadows(size, bd, tune):
 
 def test_fused_batches_and_tile_sets():
     """vhx_trace_primary_batch and vhx_trace_tiles_batch with a light (always the batch schedule: fused) against the
-    separate traces of each frame; tile padding entries stay untouched in both."""
+    separate traces of each frame; tile padding entries (tests/_tilemask.py) keep the caller's bytes in every field."""
     import torch
     size, W, H, T = 256, 200, 136, 64
     flat = vhx.FlatTree.build_scene(N.VHX_SCENE_LATTICE_CUBE, size, 4)
@@ -113,9 +114,15 @@ def test_fused_batches_and_tile_sets():
             ref = _separate(sep, cam, light, tile_size=T, tile_start=starts[k], tile_stride=stride,
                             layout=N.VHX_LAYOUT_TILES)
             got = _host(touts[k])
-            pad = ref["value"] == N.VHX_EMPTY  # padding and misses: shadowed 0 from the separate path's clear
-            got["shadowed"] = np.where(pad & (got["shadowed"] == 7), 0, got["shadowed"])
-            _assert_same(got, ref, f"tile set {k}")
+            # padding (by geometry) still holds what _outs filled in, in every field; every other entry, primary misses
+            # included, equals the separate path's
+            owned, _ = tile_mask(W, H, T, starts[k], stride, N.VHX_LAYOUT_TILES)
+            assert owned.size == sizes[k] and 0 < owned.sum() < owned.size
+            fill = {"value": 0xFFFFFFFF, "depth": 0, "rgba": 0, "shadowed": 7}
+            for f in FIELDS:
+                bad = int(np.count_nonzero(got[f][~owned] != fill[f]))
+                assert bad == 0, f"tile set {k}: field {f} written at {bad} padding entries"
+            _assert_same({f: got[f][owned] for f in FIELDS}, {f: ref[f][owned] for f in FIELDS}, f"tile set {k}")
     finally:
         sep.close()
         fus.close()

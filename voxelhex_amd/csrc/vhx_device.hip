@@ -503,6 +503,71 @@ __global__ void __launch_bounds__(256) k_emit_flags(const void *__restrict__ src
         }
 }
 
+// The output entries a primary trace owns (vhx_trace_primary's geometry: T x T tiles, tiles_x per row, the tiles
+// start, start + stride, ... of a W x H frame). Tile layout (tiles = 1): entry i is pixel i % (T * T) of the set's
+// tile i / (T * T), owned where that pixel lies inside the frame (the rest is tile padding). Framebuffer layout: entry
+// i is pixel (i % W, i / W), owned where its tile is one of the set's (the rest belongs to other ranks' calls).
+struct OwnGeom {
+    uint32_t W, H, T, tiles_x, start, stride, tiles;
+};
+__device__ __forceinline__ bool owned_entry(const OwnGeom &g, uint64_t i) {
+    if (g.tiles) {
+        const uint64_t tt = (uint64_t)g.T * g.T, j = i / tt;
+        const uint32_t l = (uint32_t)(i - j * tt), tile = g.start + (uint32_t)j * g.stride;
+        return (tile % g.tiles_x) * g.T + l % g.T < g.W && (tile / g.tiles_x) * g.T + l / g.T < g.H;
+    }
+    const uint32_t py = (uint32_t)(i / g.W), px = (uint32_t)(i - (uint64_t)py * g.W);
+    const uint32_t tile = (py / g.T) * g.tiles_x + px / g.T;
+    return tile >= g.start && (tile - g.start) % g.stride == 0u;
+}
+// hit flags of the owned entries among i..i+3 (output-index order), and the owned entries of `clear` zeroed
+__device__ __forceinline__ uint32_t owned_hit_bits(const uint32_t *value, const OwnGeom &g, uint64_t i, uint64_t n,
+                                                   uint32_t *clear = nullptr) {
+    uint32_t bits = 0;
+    for (uint64_t k = i; k < n && k < i + 4u; ++k) {
+        if (!owned_entry(g, k)) continue;
+        if (clear) clear[k] = 0u;
+        if (value[k] != VHX_EMPTY) bits |= 1u << (k - i);
+    }
+    return bits;
+}
+// k_count_flags<true> / k_emit_flags<true> over the entries a primary trace owns, for the shadow rays that follow it
+// inside vhx_trace_primary and the batches (a light set, shadows not fused): entries outside `g` are neither read,
+// cleared nor listed. Output-index order.
+__global__ void __launch_bounds__(256) k_count_owned_hits(const uint32_t *__restrict__ value, uint64_t n,
+                                                          uint32_t *__restrict__ counts, uint32_t *zero,
+                                                          uint32_t *__restrict__ clear, OwnGeom g) {
+    __shared__ uint32_t s_cnt[4];
+    if (blockIdx.x == 0)
+        for (uint32_t w = threadIdx.x; w < QCTL_WORDS - 16u; w += blockDim.x) zero[w] = 0u;
+    const uint64_t i = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 4u;
+    uint32_t c = __popc(owned_hit_bits(value, g, i, n, clear));
+    for (uint32_t d = 32; d > 0; d >>= 1) c += __shfl_down(c, d);
+    if ((threadIdx.x & 63u) == 0) s_cnt[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+__global__ void __launch_bounds__(256) k_emit_owned_hits(const uint32_t *__restrict__ value, uint64_t n,
+                                                         const uint32_t *__restrict__ offsets,
+                                                         uint32_t *__restrict__ out, OwnGeom g) {
+    __shared__ uint32_t s_wave[4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t i = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 4u;
+    const uint32_t bits = owned_hit_bits(value, g, i, n);
+    const uint32_t c = __popc(bits);
+    uint32_t inc = c;
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint32_t x = __shfl_up(inc, d);
+        if (lane >= d) inc += x;
+    }
+    if (lane == 63) s_wave[wave] = inc;
+    __syncthreads();
+    uint32_t o = offsets[blockIdx.x] + inc - c;
+    for (uint32_t w = 0; w < wave; ++w) o += s_wave[w];
+    for (uint32_t k = 0; k < 4; ++k)
+        if (bits & (1u << k)) out[o++] = (uint32_t)(i + k);
+}
+
 // One wave per chunk: copies the chunk's list to the queue at its offset; in the queue-state mode (st_q) the listed
 // rays' saved states too, from their list slots to their queue positions (64 B each, coalesced both ways), so that the
 // next pass reads a ray's state at its queue position, in the same load round as its output index.
@@ -539,6 +604,10 @@ __global__ void __launch_bounds__(256) k_gather_chunks(const uint32_t *__restric
 // in queue order, so that a wave's 64 rays start their first node iteration together and at the same node loads, while
 // the segments keep the queue's 2-D order. Bitonic sort of {node, position} keys in LDS; the queue length is read on the
 // device, and the workgroups stride over its segments. Only the order of the queue changes, never a result.
+// A fused trace (vhx_set_shadow_light) tags the entry of a leftover shadow ray with VHX_QSHADOW (bit 31; a trace of
+// 2^31 rays or more runs a single pass and queues nothing): the state index is the entry without the tag, and the
+// entry keeps its tag through the sort.
+#define VHX_QSHADOW 0x80000000u
 #define QSORT_THREADS 256u
 __global__ void __launch_bounds__(QSORT_THREADS) k_sort_segments(uint32_t *__restrict__ q, const uint32_t *n_ptr,
                                                                  const uint32_t *__restrict__ state, uint32_t seg) {
@@ -552,7 +621,7 @@ __global__ void __launch_bounds__(QSORT_THREADS) k_sort_segments(uint32_t *__res
             unsigned long long k = ~0ull;  // past the queue's end: sorts last, never written back
             if (i < cnt) {
                 v = q[base + i];
-                k = ((unsigned long long)state[16ull * v + 12u] << 32) | i;
+                k = ((unsigned long long)state[16ull * (v & ~VHX_QSHADOW) + 12u] << 32) | i;
             }
             key[i] = k;
             val[i] = v;
@@ -727,8 +796,8 @@ __device__ __forceinline__ void zero_ctl(uint32_t *zero) {
 // finished goes on, in the same pass, with the hit's shadow ray -- the shadow semantics of vhx_trace_shadows (from
 // impact + normal * 1e-3 toward the light) -- while the nodes of the hit's descent are still in this
 // CU's caches. A shadow ray abandoned at the pass budget saves its state at its pixel's index (the primary ray's is
-// done by then) and is listed with VHX_QSHADOW; a queue pass recomputes its ray from the stored hit record.
-#define VHX_QSHADOW 0x80000000u
+// done by then) and is listed with VHX_QSHADOW (defined above k_sort_segments); a queue pass recomputes its ray from
+// the stored hit record.
 __device__ __forceinline__ void hit_shadow_ray(const PassQ &q, float ix, float iy, float iz, float nx, float ny,
                                                float nz, F3d &o, F3d &d) {
     o = mk(ix + nx * 1e-3f, iy + ny * 1e-3f, iz + nz * 1e-3f);  // shadow_ray's op order
@@ -1718,6 +1787,24 @@ static int compact_flags(vhx_ctx *c, const void *src, uint64_t npos, const FlagO
     return VHX_OK;
 }
 
+// compact_flags<true> over the entries of `value` that the primary trace of geometry `own` wrote: its hits listed at
+// `out` in output-index order, their number at *total, and `clear` zeroed at the owned entries only
+static int compact_owned_hits(vhx_ctx *c, const uint32_t *value, uint64_t n, const OwnGeom &own, uint32_t *total,
+                              uint32_t *out, uint32_t *clear) {
+    const unsigned nb = (unsigned)((n + 1023) / 1024);
+    if ((uint64_t)nb * 4 > c->counts.bytes || (uint64_t)nb * 4 > c->offsets.bytes) {
+        const int rc = ensure_lists(c, nb);
+        if (rc) return rc;
+    }
+    uint32_t *counts = (uint32_t *)c->counts.ptr, *offsets = (uint32_t *)c->offsets.ptr;
+    k_count_owned_hits<<<nb, 256, 0, c->stream>>>(value, n, counts, (uint32_t *)c->qctl.ptr + 16, clear, own);
+    launch_scan(c, counts, nb, nullptr, 1, offsets, total, nb);
+    k_emit_owned_hits<<<nb, 256, 0, c->stream>>>(value, n, offsets, out, own);
+    VHX_HIP(c, hipGetLastError());
+    debug_passes(c, "compacted owned hits");
+    return VHX_OK;
+}
+
 // A trace's queue passes (launch_queue_passes): what they trace, and how pass 0 handed over its abandoned rays
 struct QueueRun {
     CamD cam{};
@@ -2067,6 +2154,10 @@ int vhx_set_pass_budgets(vhx_ctx *c, const uint32_t *budgets, uint32_t n) {
     return VHX_OK;
 }
 
+static int trace_shadows_of(vhx_ctx *c, const float light[3], uint64_t n, const uint32_t *value, const float *impact,
+                            const float *normal, uint32_t *shadowed, uint32_t *rgba, uint32_t *bytes,
+                            const OwnGeom *own);
+
 static CamD cam_of(const vhx_camera *cam) {
     CamD d;
     d.model = cam->ray_model;
@@ -2129,6 +2220,13 @@ int vhx_trace_primary(vhx_ctx *c, const vhx_camera *cam, uint32_t T, uint32_t ti
     if (shadows && (!out->value || !out->impact || !out->normal || !out->shadowed || out->bytes || t.mips || c->prepass))
         return fail(c, VHX_E_INVALID_ARG, "vhx_trace_primary with a shadow light: value, impact, normal and shadowed "
                                           "outputs needed; no byte counting, node MIPs or depth prepass");
+    // the shadow rays read the hit records while shadowed and rgba are written, fused or after the primary rays:
+    // refused here, before any launch, whichever schedule the trace would take (host outputs are staged apart)
+    if (shadows && on_device &&
+        ranges_meet({{out->shadowed, nout * 4}, {out->rgba, nout * 4}},
+                    {{out->value, nout * 4}, {out->impact, nout * 12}, {out->normal, nout * 12}}))
+        return fail(c, VHX_E_INVALID_ARG, "vhx_trace_primary with a shadow light: shadowed and rgba must not overlap "
+                                          "value, impact, normal or each other");
     uint32_t npass = 1;
     if ((rc = prepare_passes(c, nout, nblocks, npass))) return rc;
     // pass 0's list buffers for either schedule's queue order: a context's first frames often run alone (the idle
@@ -2209,9 +2307,12 @@ int vhx_trace_primary(vhx_ctx *c, const vhx_camera *cam, uint32_t T, uint32_t ti
     if (shadows && !p0.fuse) {
         // the frame's shadow rays after its primary rays (vhx_trace_shadows on the same stream); the frame's time then
         // spans both (ev0 of the primary trace, ev1 re-recorded by the shadow trace)
+        // over the entries this trace wrote: a whole framebuffer frame owns them all; tile padding and, in a
+        // rank-sharded framebuffer, the other ranks' pixels hold no record of this call and stay as they are
+        const OwnGeom own{cam->width, cam->height, T, tiles_x, tile_start, tile_stride, fb ? 0u : 1u};
         c->keep_ev0 = true;
-        rc = vhx_trace_shadows(c, c->shadow_light, nout, ho.dev.value, ho.dev.impact, ho.dev.normal, ho.dev.shadowed,
-                               ho.dev.rgba, nullptr);
+        rc = trace_shadows_of(c, c->shadow_light, nout, ho.dev.value, ho.dev.impact, ho.dev.normal, ho.dev.shadowed,
+                              ho.dev.rgba, nullptr, whole_fb ? nullptr : &own);
         c->keep_ev0 = false;
         if (rc) return rc;
     }
@@ -2257,6 +2358,7 @@ static int trace_batch(vhx_ctx *c, const vhx_camera *cams, uint32_t n, const vhx
             const void *f[7] = {o.value, o.cell, o.rgba, o.depth, o.voxel, o.impact, o.normal};
             const uint64_t w[7] = {1, 1, 1, 1, 3, 3, 3};
             for (int j = 0; j < 7; ++j) written.push_back({f[j], ent * 4 * w[j]});
+            if (c->shadow_on) written.push_back({o.shadowed, ent * 4});  // without a light it is ignored
         }
         if (ranges_meet(written, {}))
             return fail(c, VHX_E_INVALID_ARG, std::string(fn) + ": output arrays overlap each other");
@@ -2357,9 +2459,11 @@ static int trace_batch(vhx_ctx *c, const vhx_camera *cams, uint32_t n, const vhx
         c->keep_ev0 = true;
         for (uint32_t k = 0; k < n && !rc; ++k) {
             const uint64_t ent = T ? set_tiles(k) * T * T : npix;
+            // a tile set owns its in-frame entries only (tile padding stays as it is), a whole frame all of them
+            const OwnGeom own{W, H, T, tiles_x, T ? starts[k] : 0u, stride, 1u};
             if (ent)
-                rc = vhx_trace_shadows(c, c->shadow_light, ent, outs[k].value, outs[k].impact, outs[k].normal,
-                                       outs[k].shadowed, outs[k].rgba, nullptr);
+                rc = trace_shadows_of(c, c->shadow_light, ent, outs[k].value, outs[k].impact, outs[k].normal,
+                                      outs[k].shadowed, outs[k].rgba, nullptr, T ? &own : nullptr);
         }
         c->keep_ev0 = false;
     }
@@ -2500,8 +2604,12 @@ static FlagOrder shadow_order(const vhx_ctx *c, uint64_t n, uint32_t frames, uin
     return ord;
 }
 
-int vhx_trace_shadows(vhx_ctx *c, const float light[3], uint64_t n, const uint32_t *value, const float *impact,
-                      const float *normal, uint32_t *shadowed, uint32_t *rgba, uint32_t *bytes) {
+// vhx_trace_shadows; own (the shadow rays that follow a primary trace inside vhx_trace_primary and the batches): only
+// the entries that trace owns are read, cleared, listed and written -- tile padding and other ranks' pixels stay as
+// they are. Null: every i < n, the public contract, through the same kernels as ever.
+static int trace_shadows_of(vhx_ctx *c, const float light[3], uint64_t n, const uint32_t *value, const float *impact,
+                            const float *normal, uint32_t *shadowed, uint32_t *rgba, uint32_t *bytes,
+                            const OwnGeom *own) {
     if (!c || !light || (n && (!value || !impact || !normal || !shadowed))) return VHX_E_INVALID_ARG;
     if (!c->tree->uploaded) return fail(c, VHX_E_STATE, "vhx_trace_shadows before vhx_upload_tree");
     if (n == 0) return VHX_OK;
@@ -2540,8 +2648,11 @@ int vhx_trace_shadows(vhx_ctx *c, const float light[3], uint64_t n, const uint32
     // wave-dense secondary rays: the hit pixels, in the frame's queue order, are pass 0's queue
     uint64_t npos = 0;
     const FlagOrder ord = shadow_order(c, n, 1, npos);
-    if ((rc = compact_flags<true>(c, value, npos, ord, (uint32_t *)c->qctl.ptr + 7, (uint32_t *)c->queue[1].ptr, shadowed, n)))
-        return rc;
+    if (own)
+        rc = compact_owned_hits(c, value, n, *own, (uint32_t *)c->qctl.ptr + 7, (uint32_t *)c->queue[1].ptr, shadowed);
+    else
+        rc = compact_flags<true>(c, value, npos, ord, (uint32_t *)c->qctl.ptr + 7, (uint32_t *)c->queue[1].ptr, shadowed, n);
+    if (rc) return rc;
     int qrc = VHX_OK;
     const bool bd_ok = dispatch_variant(c->tree->desc.brick_dim, t.mips != nullptr, bytes != nullptr, false, false,
                                         [&](auto bd_tag, auto v) {
@@ -2550,6 +2661,11 @@ int vhx_trace_shadows(vhx_ctx *c, const float light[3], uint64_t n, const uint32
     });
     if (!bd_ok) return fail(c, VHX_E_INVALID_ARG, "unsupported brick_dim");
     return tr.end(qrc);
+}
+
+int vhx_trace_shadows(vhx_ctx *c, const float light[3], uint64_t n, const uint32_t *value, const float *impact,
+                      const float *normal, uint32_t *shadowed, uint32_t *rgba, uint32_t *bytes) {
+    return trace_shadows_of(c, light, n, value, impact, normal, shadowed, rgba, bytes, nullptr);
 }
 
 int vhx_trace_shadows_batch(vhx_ctx *c, const float light[3], uint32_t nf, uint64_t n, const vhx_shadow_frame *frames) {
