@@ -221,6 +221,17 @@ int vhx_build_tree_dense(vhx_ctx *ctx, const vhx_dense_desc *grid, int on_device
  * a leaf whose bricks are all the same Solid brick, or whose aligned 4x4x4 voxel blocks are all homogeneous, a
  * UniformLeaf holding one brick. Contract, ordering and errors as vhx_build_tree_dense. */
 int vhx_build_tree_dense_simplified(vhx_ctx *ctx, const vhx_dense_desc *grid, int on_device);
+/* vhx_build_tree_dense for a grid that carries user data beside its colours: the seven buffers and counts of
+ * vhx_dense_build_data(grid, data, 0) (vhx_boxtree.h, which states the rule) + vhx_upload_tree, bit for bit. `data` is a
+ * second plane with the extents and indexing of grid->albedo, 0 = no data, and lives where grid->albedo lives (host or
+ * device, by on_device; read in place, never written). A voxel is Visual (colour index | 0xFFFF0000), Informative
+ * (0xFFFF | data index << 16; alpha byte 0 and a data value: the colour never reaches the palette) or Complex (colour
+ * index | data index << 16); nodes and bricks exist where any of the three lies below them; data_palette holds the data
+ * values in first-appearance order of the insert loop, counted on its own. data == NULL: the call is
+ * vhx_build_tree_dense. There is no simplified variant: vhx_simplify_tree after this call gives the image of
+ * vhx_dense_build_data(grid, data, 1). Contract, ordering and errors as vhx_build_tree_dense; more than 65,535 distinct
+ * data values: VHX_E_CAPACITY, and a failing build leaves the context's previous tree as it was. */
+int vhx_build_tree_dense_data(vhx_ctx *ctx, const vhx_dense_desc *grid, const uint32_t *data, int on_device);
 #define VHX_BUF_NODE_TYPE 0
 #define VHX_BUF_NODE_OCBITS 1
 #define VHX_BUF_NODE_CHILDREN 2
@@ -290,6 +301,14 @@ typedef struct vhx_dense_out {
  * empty regions and Solid bricks are constant fills, Parted bricks are copied through the palette. on_device, ordering
  * and errors as vhx_get_voxels; a refused call leaves albedo untouched. */
 int vhx_read_dense(vhx_ctx *ctx, const vhx_dense_out *box, int on_device);
+/* vhx_read_dense with the data plane: for every voxel of the box, with v = vhx_get_voxels(position) and di = v >> 16,
+ * data[i] = data_palette[di] when v is not VHX_EMPTY and di is neither 0xFFFF nor past the palette; else 0. `data` has the
+ * extents and indexing of box->albedo and lives where it lives. box->albedo may be NULL (data only); otherwise it is
+ * filled exactly as vhx_read_dense fills it, in the same walk of the tree. on_device = 1: the two planes must not
+ * overlap (VHX_E_INVALID_ARG before anything is written). So vhx_read_dense_data of vhx_build_tree_dense_data(g, d) is
+ * (g with its alpha-0 words zeroed, d), zero-extended to the box, also after vhx_simplify_tree. Ordering and errors as
+ * vhx_read_dense; a refused call leaves both planes untouched. */
+int vhx_read_dense_data(vhx_ctx *ctx, const vhx_dense_out *box, uint32_t *data, int on_device);
 /* A box of the tree replaced by a dense albedo grid, on the device and in place: the inverse of vhx_read_dense, and the
  * counterpart of BoxTree::insert / clear for a tree without a host tree behind it. */
 #define VHX_WRITE_REPLACE 0u  /* every voxel of the box becomes the grid's; alpha byte 0 = no voxel (clears) */
@@ -314,8 +333,24 @@ typedef struct vhx_dense_in {
  * submitted before it see the old tree, frames after it the new one; returns when the tree is ready. A refused call
  * leaves the tree as it was: VHX_E_STATE before any upload, while node MIPs are set, or when the tree under the box is
  * not of canonical depth (a LOD-cut or streamed view); VHX_E_CAPACITY past 65,535 colours, 2^31 bricks or 2^28 touched
- * leaf cubes; VHX_E_INVALID_ARG for a bad box or mode. */
+ * leaf cubes; VHX_E_INVALID_ARG for a bad box or mode. On a tree with data values the call behaves as described (cells
+ * outside the box keep their data halves), and the "bit for bit a fresh build" closure with vhx_simplify_tree /
+ * vhx_compact_tree and vhx_compact_palette holds for such a tree up to the order of data_palette. */
 int vhx_write_dense(vhx_ctx *ctx, const vhx_dense_in *box, int on_device);
+/* vhx_write_dense with user data. Every voxel of the box has an albedo word a (box->albedo, or box->fill where that is
+ * NULL) and a data word d (`data`, a plane with the extents and indexing of box->albedo that lives where it lives, or
+ * fill_data where `data` is NULL; 0 = no data), and its entry follows the rule of vhx_build_tree_dense_data: none,
+ * Visual, Informative (alpha byte 0 and d != 0) or Complex. VHX_WRITE_REPLACE: every voxel of the box becomes its entry,
+ * none clears it; VHX_WRITE_INSERT: a voxel without an entry leaves the tree's voxel as it is. A written voxel is
+ * replaced wholesale in both modes, as BoxTree::insert replaces it: an old data value does not survive under a new
+ * Visual entry, nor an old colour under a new Informative one. Afterwards vhx_get_voxels of a written voxel is
+ * ci | di << 16 with 0xFFFF for a half that is none, ci / di the lowest index that holds the colour / data value; new
+ * data values are appended after data_count in the order in which new colours are appended after color_count (the
+ * box's insert order), data_palette grows like the other buffers and vhx_tree_counts reports the new data_count. An
+ * entry of data_palette equal to 0 is never matched. data == NULL and fill_data == 0: the call is vhx_write_dense, bit
+ * for bit. Past 65,535 data values: VHX_E_CAPACITY, tree unchanged. Everything else -- Leaf nodes, Parted bricks,
+ * unlinked slots, ordering, owner only, refusals -- is vhx_write_dense's contract. */
+int vhx_write_dense_data(vhx_ctx *ctx, const vhx_dense_in *box, const uint32_t *data, uint32_t fill_data, int on_device);
 /* Node and brick slots that vhx_write_dense has unlinked since the last upload or build. */
 int vhx_tree_orphans(const vhx_ctx *ctx, uint32_t *nodes, uint32_t *bricks);
 /* Rewrites the resident tree on the device without its unreachable slots and in the builders' numbering: the image of
@@ -350,7 +385,8 @@ int vhx_compact_tree(vhx_ctx *ctx, uint32_t *nodes_dropped, uint32_t *bricks_dro
  * vhx_read_dense of any box is unchanged. vhx_get_voxels is unchanged except at a position whose stored
  * value points to empty without being VHX_EMPTY, which may now read raw (under a UniformLeaf) or empty, as described
  * for those node kinds above. Traces are those of the new image: a hit in a Solid brick reports the brick's cube, no
- * cell, and an impact computed on that cube.
+ * cell, and an impact computed on that cube. On a tree with data values the call behaves the same (a brick is Solid
+ * where its cells are one value in both halves), and the closure above holds up to the order of data_palette as well.
  * Contract as vhx_compact_tree: out of place through new buffers at the new counts (peak device memory the old tree
  * plus the new one), nothing of the old tree written, a refused call or a failed allocation leaves it bit for bit as it
  * was; owner context only (VHX_E_STATE on a shared one); frames submitted before it trace the old buffers, frames after
@@ -378,7 +414,9 @@ int vhx_simplify_tree(vhx_ctx *ctx, uint32_t *nodes_dropped, uint32_t *bricks_dr
  * unchanged; `value`, from a trace or vhx_get_voxels, is the old one through the map. So after vhx_write_dense calls,
  * vhx_simplify_tree and this call leave exactly the image vhx_build_tree_dense_simplified gives for the same voxels,
  * vhx_compact_tree and this call the image of vhx_build_tree_dense, and a palette that an editing session has filled
- * with colours no voxel holds any more (VHX_E_CAPACITY from vhx_write_dense) has room again.
+ * with colours no voxel holds any more (VHX_E_CAPACITY from vhx_write_dense) has room again. On a tree with data
+ * values the call behaves the same, and "exactly the image of the build" holds up to the order of data_palette, which no
+ * call canonicalises.
  * The tree is only read until the one readback of the counters, so a refused call leaves it bit for bit as it was:
  * VHX_E_STATE before any upload, on a shared context, while node MIPs are set (MIP bricks are not reachable through
  * the entries, their colours would be dropped), and for a malformed tree (vhx_compact_tree's cases, a Solid entry at

@@ -154,6 +154,23 @@ int vhx_dense_build_tree(const vhx_dense_desc *grid, int threads, vhx_boxtree **
  * are the same Solid brick or every aligned 4x4x4 block of their voxels is homogeneous. vhx_build_tree_dense_simplified
  * (vhx.h) writes the same image on the GPU. Errors as vhx_dense_build. */
 int vhx_dense_build_simplified(const vhx_dense_desc *grid, int threads, vhx_flat **out);
+/* The bulk builders for a dense grid that carries user data beside its colours. `data` is a second plane with the
+ * extents and indexing of grid->albedo: voxel (x,y,z) at data[((uint64_t)z*gy + y)*gx + x], 0 = no data (is_empty of
+ * T = u32). Per voxel, with a the albedo word and d the data word:
+ *   alpha byte of a == 0, d == 0   no entry (skipped)
+ *   alpha byte of a != 0, d == 0   Visual(a):       value  ci | 0xFFFF0000
+ *   alpha byte of a == 0, d != 0   Informative(d):  value  0xFFFF | di << 16  (a never reaches the colour palette)
+ *   alpha byte of a != 0, d != 0   Complex(a, d):   value  ci | di << 16
+ * ci / di index color_palette / data_palette, 0xFFFF = none. The image is the one vhx_boxtree_insert of every voxel that
+ * has an entry, with that kind, in x-outer, y, z-inner order and vhx_boxtree_flatten give: each palette in
+ * first-appearance order of that loop, counted per palette on its own; a node or brick exists where any entry lies
+ * below it, a data-only one included. simplified = 1: that tree after vhx_boxtree_simplify(tree, recursive = 1), as
+ * vhx_dense_build_simplified (a brick is Solid where all its cells hold one value, both halves). data == NULL: the call
+ * is vhx_dense_build / vhx_dense_build_simplified, bit for bit. Errors as vhx_dense_build; more than 65,535 distinct
+ * data values: VHX_E_CAPACITY. vhx_build_tree_dense_data (vhx.h) writes the plain image on the GPU. */
+int vhx_dense_build_data(const vhx_dense_desc *grid, const uint32_t *data, int simplified, int threads, vhx_flat **out);
+/* The host BoxTree of that image, as vhx_dense_build_tree; data == NULL: vhx_dense_build_tree. */
+int vhx_dense_build_tree_data(const vhx_dense_desc *grid, const uint32_t *data, int threads, vhx_boxtree **out);
 int vhx_flat_node_mips(const vhx_flat *flat, const uint32_t **node_mips, uint32_t *count);
 /* Fills *desc with pointers into the flat object (valid until vhx_flat_free). */
 int vhx_flat_desc(const vhx_flat *flat, vhx_tree_desc *desc);

@@ -130,6 +130,9 @@ SIGNATURES = [
     ("vhx_get_voxels", c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_int]),
     ("vhx_read_dense", c_int, [c_void_p, P(DenseOut), c_int]),
     ("vhx_write_dense", c_int, [c_void_p, P(DenseIn), c_int]),
+    ("vhx_build_tree_dense_data", c_int, [c_void_p, P(DenseDesc), c_void_p, c_int]),
+    ("vhx_read_dense_data", c_int, [c_void_p, P(DenseOut), c_void_p, c_int]),
+    ("vhx_write_dense_data", c_int, [c_void_p, P(DenseIn), c_void_p, c_u32, c_int]),
     ("vhx_tree_orphans", c_int, [c_void_p, P(c_u32), P(c_u32)]),
     ("vhx_compact_tree", c_int, [c_void_p, P(c_u32), P(c_u32)]),
     ("vhx_simplify_tree", c_int, [c_void_p, P(c_u32), P(c_u32)]),
@@ -206,6 +209,8 @@ SIGNATURES = [
     ("vhx_dense_build", c_int, [P(DenseDesc), c_int, P(c_void_p)]),
     ("vhx_dense_build_tree", c_int, [P(DenseDesc), c_int, P(c_void_p)]),
     ("vhx_dense_build_simplified", c_int, [P(DenseDesc), c_int, P(c_void_p)]),
+    ("vhx_dense_build_data", c_int, [P(DenseDesc), c_void_p, c_int, c_int, P(c_void_p)]),
+    ("vhx_dense_build_tree_data", c_int, [P(DenseDesc), c_void_p, c_int, P(c_void_p)]),
     ("vhx_flat_desc", c_int, [c_void_p, P(TreeDesc)]),
     ("vhx_flat_compact", c_int, [P(TreeDesc), P(c_void_p)]),
     ("vhx_flat_simplify", c_int, [P(TreeDesc), P(c_void_p)]),

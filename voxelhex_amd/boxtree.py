@@ -274,6 +274,20 @@ def _dense_desc(grid, size, brick_dim):
     return d, g
 
 
+def _dense_data(data, shape):
+    """The data plane of a dense grid of `shape`: a C-contiguous uint32 array (0 = no data), or None."""
+    if data is None:
+        return None
+    p = np.asarray(data)
+    if p.dtype != np.uint32 or tuple(p.shape) != tuple(shape):
+        raise TypeError(f"a data plane is a uint32 array of the grid's shape {tuple(shape)}")
+    return np.ascontiguousarray(p)
+
+
+def _u32_ptr(a):
+    return None if a is None else a.ctypes.data
+
+
 def _compacted(image):
     """vhx_flat_compact of a FlatTree or TreeImage, as a new FlatTree."""
     h = ctypes.c_void_p()
@@ -458,16 +472,24 @@ class FlatTree:
         return FlatTree(h.value)
 
     @staticmethod
-    def from_dense(grid, size, brick_dim, threads=0, simplify=False):
+    def from_dense(grid, size, brick_dim, threads=0, simplify=False, data=None):
         """Bulk-builds the canonical tree of a dense grid (vhx_dense_build): `grid` is a uint32 numpy array of shape
         (gz, gy, gx) of packed albedos r | g<<8 | b<<16 | a<<24 (alpha 0 = no voxel) sitting at the tree's origin. The
         image equals inserting every voxel (x outer, y, z inner) into BoxTree(size, brick_dim) and flattening; with
-        simplify=True, simplifying the tree recursively before flattening (vhx_dense_build_simplified)."""
+        simplify=True, simplifying the tree recursively before flattening (vhx_dense_build_simplified).
+        `data` (optional) is a uint32 array of the same shape with a user data value per voxel, 0 = none
+        (vhx_dense_build_data): a voxel with a colour and a data value is a Complex entry, one with a data value and
+        alpha 0 an Informative entry, and data_palette lists the values in first-appearance order of the insert loop."""
         d, keep = _dense_desc(grid, size, brick_dim)
+        plane = _dense_data(data, keep.shape)
         h = ctypes.c_void_p()
+        what = f"dense grid {keep.shape[::-1]} size {size} brick_dim {brick_dim}"
+        if plane is not None:
+            _tree_check(N.lib().vhx_dense_build_data(ctypes.byref(d), _u32_ptr(plane), 1 if simplify else 0, threads,
+                                                     ctypes.byref(h)), what)
+            return FlatTree(h.value)
         build = N.lib().vhx_dense_build_simplified if simplify else N.lib().vhx_dense_build
-        _tree_check(build(ctypes.byref(d), threads, ctypes.byref(h)),
-                    f"dense grid {keep.shape[::-1]} size {size} brick_dim {brick_dim}")
+        _tree_check(build(ctypes.byref(d), threads, ctypes.byref(h)), what)
         return FlatTree(h.value)
 
     def counts(self):
@@ -519,12 +541,14 @@ class BoxTree:
         return cls._from_handle(h)
 
     @classmethod
-    def from_dense(cls, grid, size, brick_dim, threads=0):
+    def from_dense(cls, grid, size, brick_dim, threads=0, data=None):
         """The tree that inserting every voxel of a dense grid (FlatTree.from_dense) builds, from the bulk builder's
-        image (vhx_dense_build_tree); occlusion bits and MIP maps are not restored, as for from_scene."""
+        image (vhx_dense_build_tree; with a `data` plane vhx_dense_build_tree_data); occlusion bits and MIP maps are not
+        restored, as for from_scene."""
         d, keep = _dense_desc(grid, size, brick_dim)
+        plane = _dense_data(data, keep.shape)
         h = ctypes.c_void_p()
-        _tree_check(N.lib().vhx_dense_build_tree(ctypes.byref(d), threads, ctypes.byref(h)),
+        _tree_check(N.lib().vhx_dense_build_tree_data(ctypes.byref(d), _u32_ptr(plane), threads, ctypes.byref(h)),
                     f"dense grid {keep.shape[::-1]} size {size} brick_dim {brick_dim}")
         return cls._from_handle(h)
 

@@ -132,9 +132,11 @@ struct vhx_ctx {
     // every possible node per level (the leaves' are their brick masks), their breadth-first ranks and first brick
     // indices, the scans' block sums, the colour table with the palette ranked from it, the counters read back, and the
     // device copy of a host grid; for vhx_build_tree_dense_simplified also the leaves' Parted masks and classes and the
-    // ranked solid values (simp)
+    // ranked solid values (simp); for the calls that carry a data plane (vhx_build_tree_dense_data,
+    // vhx_write_dense_data) a second table of the colour table's shape for the data values (dtable), whose counters
+    // follow the colours' in ctl, and the data plane of a host grid behind its albedo plane in grid
     struct BuildScratch {
-        DevBuf occ, rank, first, part, table, ctl, grid, simp;
+        DevBuf occ, rank, first, part, table, ctl, grid, simp, dtable;
     } build;
     // vhx_write_dense (vhx_edit.hip): per level of the box's lattice of aligned cubes the old node of every cube, its
     // occupancy after the write, the "needs a new node" words with their ranks, the leaves' new-brick masks and first

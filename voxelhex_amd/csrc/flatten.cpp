@@ -337,6 +337,19 @@ struct DenseSource {
         return (c >> 24) ? c : 0;  // alpha 0: BoxTreeEntry::is_none of a Visual entry (boxtree.cpp entry_is_none)
     }
 };
+// A dense grid with a data plane beside the albedo plane: voxel() is the albedo (0 where its alpha byte is 0) in the low
+// word and the data value (0 = none, is_empty of T = u32) in the high word, so 0 is still "no entry": the albedo alone
+// is a Visual entry, the data alone an Informative one, both a Complex one.
+struct DenseDataSource {
+    const uint32_t *albedo, *data;
+    uint32_t ex, ey, ez;
+    inline uint64_t voxel(uint32_t x, uint32_t y, uint32_t z) const {
+        if (x >= ex || y >= ey || z >= ez) return 0;
+        const uint64_t at = ((uint64_t)z * ey + y) * ex + x;
+        const uint32_t c = albedo[at];
+        return (uint64_t)((c >> 24) ? c : 0u) | ((uint64_t)data[at] << 32);
+    }
+};
 
 // Palette in first-appearance order of the reference insert loop (x outer, y, z inner), slab by slab: the order a
 // procedural scene is evaluated in.
@@ -362,14 +375,16 @@ static void palette_by_slabs(const SceneSource &src, int threads, std::vector<ui
 // The same palette for a dense grid, read in memory order (x runs fastest there, and the insert loop's z-inner walk
 // would touch a cache line per voxel): every colour's smallest insert-order index (x*gy + y)*gz + z, z plane by z plane,
 // then the colours sorted by it. A voxel whose left neighbour has its colour is skipped (the neighbour's index is smaller).
-static int palette_by_first_index(const DenseSource &src, int threads, std::vector<uint32_t> &palette) {
+// `half(x, y, z)` is the colour of the voxel, or, for the data palette, its data value; 0 = none in both.
+template <class Source, class Half>
+static int palette_by_first_index(const Source &src, int threads, Half half, std::vector<uint32_t> &palette) {
     std::vector<std::unordered_map<uint32_t, uint64_t>> plane(src.ez);
     parallel_for(src.ez, threads, [&](int64_t z) {
         auto &first = plane[z];
         for (uint32_t y = 0; y < src.ey; ++y) {
             uint32_t last = 0;
             for (uint32_t x = 0; x < src.ex; ++x) {
-                const uint32_t c = src.voxel(x, y, (uint32_t)z);
+                const uint32_t c = half(x, y, (uint32_t)z);
                 if (c == last) continue;
                 last = c;
                 if (c == 0) continue;
@@ -396,7 +411,8 @@ static int palette_by_first_index(const DenseSource &src, int threads, std::vect
     return VHX_OK;
 }
 
-// Writes the canonical image of `src` into *f, whose size, brick_dim and colour palette are set.
+// Writes the canonical image of `src` into *f, whose size, brick_dim and palettes are set. A source's voxel() is the
+// albedo, with the data value in the high word where the source has a data plane.
 template <class Source>
 static int build_image(const Source &sc, int threads, vhx_flat *f) {
     const uint32_t S = f->size, bd = f->brick_dim;
@@ -408,6 +424,8 @@ static int build_image(const Source &sc, int threads, vhx_flat *f) {
 
     std::unordered_map<uint32_t, uint32_t> color_index;
     for (uint32_t c : f->color_palette) color_index.emplace(c, (uint32_t)color_index.size());
+    std::unordered_map<uint32_t, uint32_t> data_index;
+    for (uint32_t d : f->data_palette) data_index.emplace(d, (uint32_t)data_index.size());
 
     // leaf path code -> leaf coordinates (digit i of the code = sectant taken at depth i)
     auto leaf_coord = [&](uint64_t code, uint32_t &lx, uint32_t &ly, uint32_t &lz) {
@@ -486,7 +504,8 @@ static int build_image(const Source &sc, int threads, vhx_flat *f) {
         uint32_t lx, ly, lz;
         leaf_coord((uint64_t)code, lx, ly, lz);
         uint64_t b = leaf_first[code];
-        uint32_t last_c = 0, last_v = VHX_EMPTY;
+        decltype(sc.voxel(0, 0, 0)) last_c = 0;
+        uint32_t last_v = VHX_EMPTY;
         for (uint32_t s = 0; s < 64; ++s) {
             if (!((m >> s) & 1ull)) continue;
             f->node_children[(size_t)li * 64 + s] = (uint32_t)b;
@@ -495,12 +514,14 @@ static int build_image(const Source &sc, int threads, vhx_flat *f) {
             for (uint32_t z = 0; z < bd; ++z)
                 for (uint32_t y = 0; y < bd; ++y)
                     for (uint32_t x = 0; x < bd; ++x) {
-                        uint32_t c = sc.voxel(bx + x, by + y, bz + z);
+                        const auto c = sc.voxel(bx + x, by + y, bz + z);
                         uint32_t v = VHX_EMPTY;
                         if (c != 0) {
                             if (c != last_c) {
                                 last_c = c;
-                                last_v = color_index.at(c) | (0xFFFFu << 16);  // pix_visual
+                                // pix_visual, pix_informative or pix_complex: 0xFFFF for the half that is none
+                                const uint32_t a = (uint32_t)c, d = (uint32_t)((uint64_t)c >> 32);
+                                last_v = (a ? color_index.at(a) : 0xFFFFu) | ((d ? data_index.at(d) : 0xFFFFu) << 16);
                             }
                             v = last_v;
                         }
@@ -535,19 +556,29 @@ static int build_scene(uint32_t scene_id, uint32_t S, uint32_t bd, uint64_t seed
     return VHX_OK;
 }
 
-static int build_dense(const vhx_dense_desc *g, int threads, vhx_flat **out) {
+static int build_dense(const vhx_dense_desc *g, const uint32_t *data, int threads, vhx_flat **out) {
     if (!g) return VHX_E_INVALID_ARG;
     int rc = check_sizes(g->boxtree_size, g->brick_dim);
     if (rc != 0) return rc;
     const uint32_t S = g->boxtree_size;
     if (!g->albedo || g->gx == 0 || g->gy == 0 || g->gz == 0 || g->gx > S || g->gy > S || g->gz > S)
         return VHX_E_INVALID_ARG;
-    DenseSource src{g->albedo, g->gx, g->gy, g->gz};
     std::unique_ptr<vhx_flat> f(new vhx_flat());
     f->size = S;
     f->brick_dim = g->brick_dim;
-    if ((rc = palette_by_first_index(src, threads, f->color_palette)) != 0) return rc;
-    if ((rc = build_image(src, threads, f.get())) != 0) return rc;
+    if (data) {  // each palette in first-appearance order of its own half
+        DenseDataSource src{g->albedo, data, g->gx, g->gy, g->gz};
+        const auto color = [&](uint32_t x, uint32_t y, uint32_t z) { return (uint32_t)src.voxel(x, y, z); };
+        const auto datum = [&](uint32_t x, uint32_t y, uint32_t z) { return (uint32_t)(src.voxel(x, y, z) >> 32); };
+        if ((rc = palette_by_first_index(src, threads, color, f->color_palette)) != 0) return rc;
+        if ((rc = palette_by_first_index(src, threads, datum, f->data_palette)) != 0) return rc;
+        if ((rc = build_image(src, threads, f.get())) != 0) return rc;
+    } else {
+        DenseSource src{g->albedo, g->gx, g->gy, g->gz};
+        const auto color = [&](uint32_t x, uint32_t y, uint32_t z) { return src.voxel(x, y, z); };
+        if ((rc = palette_by_first_index(src, threads, color, f->color_palette)) != 0) return rc;
+        if ((rc = build_image(src, threads, f.get())) != 0) return rc;
+    }
     *out = f.release();
     return VHX_OK;
 }
@@ -930,21 +961,12 @@ int vhx_scene_build_tree(uint32_t scene, uint32_t size, uint32_t brick_dim, uint
         return VHX_E_CAPACITY;
     }
 }
-int vhx_dense_build(const vhx_dense_desc *grid, int threads, vhx_flat **out) {
-    if (!out) return VHX_E_INVALID_ARG;
-    *out = nullptr;
-    try {
-        return build_dense(grid, threads, out);
-    } catch (const std::bad_alloc &) {
-        return VHX_E_CAPACITY;
-    }
-}
-int vhx_dense_build_tree(const vhx_dense_desc *grid, int threads, vhx_boxtree **out) {
+int vhx_dense_build_tree_data(const vhx_dense_desc *grid, const uint32_t *data, int threads, vhx_boxtree **out) {
     if (!out) return VHX_E_INVALID_ARG;
     *out = nullptr;
     try {
         vhx_flat *full = nullptr;
-        int rc = build_dense(grid, threads, &full);
+        int rc = build_dense(grid, data, threads, &full);
         if (rc != VHX_OK) return rc;
         std::unique_ptr<vhx_flat> owned(full);
         BoxTree *t = tree_of_flat(*full);
@@ -955,12 +977,13 @@ int vhx_dense_build_tree(const vhx_dense_desc *grid, int threads, vhx_boxtree **
         return VHX_E_CAPACITY;
     }
 }
-int vhx_dense_build_simplified(const vhx_dense_desc *grid, int threads, vhx_flat **out) {
+int vhx_dense_build_data(const vhx_dense_desc *grid, const uint32_t *data, int simplified, int threads, vhx_flat **out) {
     if (!out) return VHX_E_INVALID_ARG;
     *out = nullptr;
     try {
+        if (!simplified) return build_dense(grid, data, threads, out);
         vhx_flat *full = nullptr;
-        int rc = build_dense(grid, threads, &full);
+        int rc = build_dense(grid, data, threads, &full);
         if (rc != VHX_OK) return rc;
         std::unique_ptr<vhx_flat> owned(full);
         std::unique_ptr<BoxTree> t(tree_of_flat(*full));
@@ -972,6 +995,15 @@ int vhx_dense_build_simplified(const vhx_dense_desc *grid, int threads, vhx_flat
     } catch (const std::bad_alloc &) {
         return VHX_E_CAPACITY;
     }
+}
+int vhx_dense_build(const vhx_dense_desc *grid, int threads, vhx_flat **out) {
+    return vhx_dense_build_data(grid, nullptr, 0, threads, out);
+}
+int vhx_dense_build_tree(const vhx_dense_desc *grid, int threads, vhx_boxtree **out) {
+    return vhx_dense_build_tree_data(grid, nullptr, threads, out);
+}
+int vhx_dense_build_simplified(const vhx_dense_desc *grid, int threads, vhx_flat **out) {
+    return vhx_dense_build_data(grid, nullptr, 1, threads, out);
 }
 int vhx_flat_desc(const vhx_flat *f, vhx_tree_desc *d) {
     if (!f || !d) return VHX_E_INVALID_ARG;

@@ -25,6 +25,12 @@
 // scan or from the first indices, so the buffers do not depend on scheduling. Grid offsets are
 // 64-bit; nothing outside [0,gx) x [0,gy) x [0,gz) is read.
 //
+// vhx_build_tree_dense_data builds from a grid with a data plane beside its albedo plane (the image of
+// vhx_dense_build_data): a voxel is an entry where it has a colour (alpha byte not 0) or a data value (not 0), its cell
+// is colour index | data index << 16 with 0xFFFF for the half that is none, and the data values get a table, a
+// compaction and a ranking of their own, exactly as the colours (counters: a second BuildCtl behind the first). The
+// passes are the same ones, instantiated with DATA = 1; the colour-only instantiations are unchanged.
+//
 // vhx_build_tree_dense_simplified writes the image BoxTree::simplify(ROOT, recursive) leaves of that tree
 // (vhx_dense_build_simplified of flatten.cpp, bit for bit). Nodes, their numbering, occupancy and the palette stay;
 // only the leaves change. A brick all of whose cells hold one colour is Solid(palette index | 0xFFFF0000); a leaf whose
@@ -78,6 +84,7 @@ struct GridP {
     uint32_t gx, gy, gz;
     uint32_t bsh;  // log2(brick_dim)
     uint32_t D;    // leaf level
+    const uint32_t *d;  // the data plane (vhx_build_tree_dense_data), indexed as a; null without one
 };
 
 // path code of the leaf with coordinates (lx, ly, lz): digit i (from the top) = the sectant taken at depth i
@@ -88,12 +95,43 @@ __device__ inline uint32_t leaf_code(uint32_t lx, uint32_t ly, uint32_t lz, uint
     return code;
 }
 
+// Pass A, the values of one plane (colours, or data values) in a thread's row j: a voxel is skipped when a voxel of its
+// value further left in its row is in this wave: that one's insert-order index is smaller. First the left neighbour and
+// the thread's own voxels; then, per value, the lowest lane of a row group records it for the group (x grows with the
+// lane there). Called by all 64 lanes.
+template <int VEC>
+__device__ __forceinline__ void scan_record(const uint32_t (&row)[VEC], bool row_start, uint32_t lane, uint32_t sub,
+                                            const GridP &g, uint32_t x0, uint32_t y, uint32_t z, ColorTable t,
+                                            BuildCtl *ctl) {
+    uint32_t left = __shfl_up(row[VEC - 1], 1);
+    if (row_start) left = 0;
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) {
+        const uint32_t c = row[i];
+        bool cand = c != 0 && c != left;
+#pragma unroll
+        for (int e = 0; e + 1 < i; ++e) cand = cand && row[e] != c;
+        left = c;
+        u64 pending = __ballot(cand);
+        while (pending) {  // the same in every lane
+            const uint32_t leader = (uint32_t)__ffsll((long long)pending) - 1u;
+            const uint32_t lc = __shfl(c, leader), lsub = __shfl(sub, leader);
+            const bool mine = cand && c == lc && sub == lsub;
+            if (lane == leader) color_insert(t, ctl, c, ((u64)(x0 + i) * g.gy + y) * g.gz + z);
+            pending &= ~__ballot(mine);
+        }
+    }
+}
+
 // Pass A. A block covers `tpr` = 2^xsh vector columns of 256 / tpr row groups; a thread reads VEC voxels consecutive in
 // x (VEC = 4: one 16-byte load; gx is then a multiple of 4 and the grid 16-byte aligned) of SCAN_ROWS = 4 rows
 // consecutive in y, starting at a multiple of 4: a leaf's edge is a multiple of 4, so all of a thread's voxels share a
 // leaf. The loops are the same for every thread of a block, so the wave operations below always run with all 64 lanes.
-template <int VEC>
-__global__ __launch_bounds__(256) void k_dense_scan(GridP g, uint32_t xsh, u64 *leaf_mask, ColorTable t, BuildCtl *ctl) {
+// DATA = 1 reads the data plane beside the albedo plane (VEC = 4: both 16-byte aligned): a voxel with a data value sets
+// its brick's bit whatever its colour, and the data values go into their own table `dt` with the counters of ctl[1].
+template <int VEC, int DATA>
+__global__ __launch_bounds__(256) void k_dense_scan(GridP g, uint32_t xsh, u64 *leaf_mask, ColorTable t, ColorTable dt,
+                                                    BuildCtl *ctl) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t tpr = 1u << xsh, rpb = 256u >> xsh;
     const uint32_t gxv = (g.gx + VEC - 1) / VEC;
@@ -107,10 +145,15 @@ __global__ __launch_bounds__(256) void k_dense_scan(GridP g, uint32_t xsh, u64 *
         for (uint32_t yt = blockIdx.y; yt < ytiles; yt += gridDim.y) {
             const uint32_t yb = (yt * rpb + sub) * SCAN_ROWS;
             uint32_t v[SCAN_ROWS][VEC];
+            uint32_t w[DATA ? SCAN_ROWS : 1][VEC];  // the data values
 #pragma unroll
             for (uint32_t j = 0; j < SCAN_ROWS; ++j) {
 #pragma unroll
                 for (int i = 0; i < VEC; ++i) v[j][i] = 0;
+                if constexpr (DATA != 0) {
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i) w[j][i] = 0;
+                }
                 if (xv < gxv && yb + j < g.gy) {
                     const uint64_t at = ((uint64_t)z * g.gy + (yb + j)) * g.gx + (uint64_t)xv * VEC;
                     if constexpr (VEC == 4) {
@@ -122,6 +165,17 @@ __global__ __launch_bounds__(256) void k_dense_scan(GridP g, uint32_t xsh, u64 *
                     } else {
                         v[j][0] = g.a[at];
                     }
+                    if constexpr (DATA != 0) {
+                        if constexpr (VEC == 4) {
+                            const uint4 q = *reinterpret_cast<const uint4 *>(g.d + at);
+                            w[j][0] = q.x;
+                            w[j][1] = q.y;
+                            w[j][2] = q.z;
+                            w[j][3] = q.w;
+                        } else {
+                            w[j][0] = g.d[at];
+                        }
+                    }
                 }
             }
             u64 m = 0;
@@ -131,32 +185,15 @@ __global__ __launch_bounds__(256) void k_dense_scan(GridP g, uint32_t xsh, u64 *
 #pragma unroll
                 for (int i = 0; i < VEC; ++i) {
                     if ((v[j][i] >> 24) == 0) v[j][i] = 0;  // alpha 0: no voxel
-                    if (v[j][i]) {
+                    bool entry = v[j][i] != 0;
+                    if constexpr (DATA != 0) entry = entry || w[j][i] != 0;  // a data-only voxel is an entry too
+                    if (entry) {
                         const uint32_t s = (((x0 + i) >> g.bsh) & 3u) | (((y >> g.bsh) & 3u) << 2) | (((z >> g.bsh) & 3u) << 4);
                         m |= 1ull << s;
                     }
                 }
-                // Colours. A voxel is skipped when a voxel of its colour further left in its row is in this wave: that
-                // one's insert-order index is smaller. First the left neighbour and the thread's own voxels; then, per
-                // colour, the lowest lane of a row group records it for the group (x grows with the lane there).
-                uint32_t left = __shfl_up(v[j][VEC - 1], 1);
-                if (row_start) left = 0;
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) {
-                    const uint32_t c = v[j][i];
-                    bool cand = c != 0 && c != left;
-#pragma unroll
-                    for (int e = 0; e + 1 < i; ++e) cand = cand && v[j][e] != c;
-                    left = c;
-                    u64 pending = __ballot(cand);
-                    while (pending) {  // the same in every lane
-                        const uint32_t leader = (uint32_t)__ffsll((long long)pending) - 1u;
-                        const uint32_t lc = __shfl(c, leader), lsub = __shfl(sub, leader);
-                        const bool mine = cand && c == lc && sub == lsub;
-                        if (lane == leader) color_insert(t, ctl, c, ((u64)(x0 + i) * g.gy + y) * g.gz + z);
-                        pending &= ~__ballot(mine);
-                    }
-                }
+                scan_record<VEC>(v[j], row_start, lane, sub, g, x0, y, z, t, ctl);
+                if constexpr (DATA != 0) scan_record<VEC>(w[j], row_start, lane, sub, g, x0, y, z, dt, ctl + 1);
             }
             // brick bits: OR over each run of lanes in the same leaf, one atomic per run, and none where the mask already
             // holds the bits (a stale read only costs the atomic)
@@ -220,12 +257,14 @@ __global__ __launch_bounds__(256) void k_emit_nodes(uint32_t lv, uint32_t D, uin
 }
 
 // One block per leaf at a time: the cells of its bricks are one contiguous run of the voxel buffer, written in order.
+// DATA = 1 gathers the data plane as well: a cell is colour index | data index << 16, 0xFFFF for a half that is none.
+template <int DATA>
 __global__ __launch_bounds__(256) void k_emit_bricks(GridP g, const u64 *leaf_mask, const u64 *first, uint64_t nleaf,
-                                                     ColorTable t, uint32_t *voxels) {
+                                                     ColorTable t, ColorTable dt, uint32_t *voxels) {
     __shared__ uint8_t sect[64];
     const uint32_t tid = threadIdx.x;
     const uint32_t bd = 1u << g.bsh, n3sh = 3 * g.bsh, lsh = g.bsh + 2;
-    uint32_t last_c = 0, last_v = VHX_EMPTY;
+    uint32_t last_c = 0, last_d = 0, last_v = VHX_EMPTY;
     for (uint64_t code = blockIdx.x; code < nleaf; code += gridDim.x) {
         const u64 m = leaf_mask[code];
         if (m == 0) continue;  // the whole block
@@ -245,13 +284,20 @@ __global__ __launch_bounds__(256) void k_emit_bricks(GridP g, const u64 *leaf_ma
             const uint32_t x = (lx << lsh) + ((s & 3u) << g.bsh) + (i & (bd - 1u));
             const uint32_t y = (ly << lsh) + (((s >> 2) & 3u) << g.bsh) + ((i >> g.bsh) & (bd - 1u));
             const uint32_t z = (lz << lsh) + ((s >> 4) << g.bsh) + (i >> (2 * g.bsh));
-            uint32_t c = 0;
-            if (x < g.gx && y < g.gy && z < g.gz) c = g.a[((uint64_t)z * g.gy + y) * g.gx + x];
+            uint32_t c = 0, d = 0;
+            if (x < g.gx && y < g.gy && z < g.gz) {
+                const uint64_t at = ((uint64_t)z * g.gy + y) * g.gx + x;
+                c = g.a[at];
+                if constexpr (DATA != 0) d = g.d[at];
+            }
+            if ((c >> 24) == 0) c = 0;  // alpha 0: no colour
             uint32_t v = VHX_EMPTY;
-            if (c >> 24) {
-                if (c != last_c) {
+            if (c | d) {
+                if (c != last_c || d != last_d) {
                     last_c = c;
-                    last_v = color_lookup(t, c) | 0xFFFF0000u;  // pix_visual: colour index, no data
+                    last_d = d;
+                    // pix_visual, pix_informative, pix_complex: 0xFFFF for the half that is none
+                    last_v = (c ? color_lookup(t, c) : 0xFFFFu) | ((d ? color_lookup(dt, d) : 0xFFFFu) << 16);
                 }
                 v = last_v;
             }
@@ -440,6 +486,7 @@ struct FillArg {
     uint64_t level_off[MAX_LEVELS];
     uint32_t level_base[MAX_LEVELS];
     uint32_t color_count;
+    uint32_t data_count;  // vhx_build_tree_dense_data; 0 without a data plane
 };
 
 // receive_tree's fill step: the emission kernels write straight into the tree's raw buffers
@@ -449,6 +496,7 @@ int fill_from_scratch(void *arg, void *const dst[7], const uint64_t bytes[7]) {
     const u64 *occ = (const u64 *)c->build.occ.ptr, *rank = (const u64 *)c->build.rank.ptr;
     const u64 *first = (const u64 *)c->build.first.ptr;
     const ColorTable t = table_of(c->build.table.ptr);
+    const ColorTable dt = a.g.d ? table_of(c->build.dtable.ptr) : ColorTable{};
     const uint32_t D = a.levels - 1;
     const uint64_t nleaf = 1ull << (6 * D);
     const SimpTable sp = a.simplified ? simp_of(c->build.simp.ptr, nleaf) : SimpTable{};
@@ -469,8 +517,12 @@ int fill_from_scratch(void *arg, void *const dst[7], const uint64_t bytes[7]) {
     if (bytes[VHX_BUF_VOXELS]) {
         const unsigned blocks = (unsigned)std::min<uint64_t>(nleaf, (uint64_t)c->cus * 16);
         // a simplified image copies the Parted bricks only
-        k_emit_bricks<<<blocks, 256, 0, c->stream>>>(a.g, a.simplified ? sp.pmask : occ + a.level_off[D], first, nleaf, t,
-                                                     (uint32_t *)dst[VHX_BUF_VOXELS]);
+        if (a.g.d)
+            k_emit_bricks<1><<<blocks, 256, 0, c->stream>>>(a.g, occ + a.level_off[D], first, nleaf, t, dt,
+                                                            (uint32_t *)dst[VHX_BUF_VOXELS]);
+        else
+            k_emit_bricks<0><<<blocks, 256, 0, c->stream>>>(a.g, a.simplified ? sp.pmask : occ + a.level_off[D], first,
+                                                            nleaf, t, dt, (uint32_t *)dst[VHX_BUF_VOXELS]);
         if (a.simplified && a.g.bsh > 0)
             k_emit_uniform<<<blocks, 256, 0, c->stream>>>(a.g, first, nleaf, t, sp, (uint32_t *)dst[VHX_BUF_VOXELS]);
         VHX_HIP(c, hipGetLastError());
@@ -481,11 +533,16 @@ int fill_from_scratch(void *arg, void *const dst[7], const uint64_t bytes[7]) {
     if (bytes[VHX_BUF_COLOR_PALETTE])
         VHX_HIP(c, hipMemcpyAsync(dst[VHX_BUF_COLOR_PALETTE], t.pal, (uint64_t)a.color_count * 4,
                                   hipMemcpyDeviceToDevice, c->stream));
+    if (a.data_count && bytes[VHX_BUF_DATA_PALETTE])
+        VHX_HIP(c, hipMemcpyAsync(dst[VHX_BUF_DATA_PALETTE], dt.pal, (uint64_t)a.data_count * 4,
+                                  hipMemcpyDeviceToDevice, c->stream));
     return VHX_OK;
 }
 
-// both entry points; `name` is the one called, for the error texts
-int build_tree(vhx_ctx *c, const vhx_dense_desc *grid, int on_device, bool simplified, const char *name) {
+// the entry points; `name` is the one called, for the error texts. `data` (null: none) lives where grid->albedo lives
+// and is not combined with `simplified`.
+int build_tree(vhx_ctx *c, const vhx_dense_desc *grid, const uint32_t *data, int on_device, bool simplified,
+               const char *name) {
     const auto fail_in = [&](int code, const char *what) { return fail(c, code, std::string(name) + what); };
     if (!c || !grid) return fail_in(VHX_E_INVALID_ARG, ": null argument");
     if (c->shared) return fail_in(VHX_E_STATE, " on a shared context: build through the owner");
@@ -533,25 +590,37 @@ int build_tree(vhx_ctx *c, const vhx_dense_desc *grid, int on_device, bool simpl
     if ((rc = vhx::ensure(c, c->build.first, nleaf * 8))) return rc;
     if ((rc = vhx::ensure(c, c->build.part, ((nleaf + SCAN_TILE - 1) / SCAN_TILE) * 8))) return rc;
     if ((rc = vhx::ensure(c, c->build.table, TAB_BYTES))) return rc;
-    if ((rc = vhx::ensure(c, c->build.ctl, sizeof(BuildCtl)))) return rc;
+    if (data && (rc = vhx::ensure(c, c->build.dtable, TAB_BYTES))) return rc;
+    if ((rc = vhx::ensure(c, c->build.ctl, 2 * sizeof(BuildCtl)))) return rc;  // [1]: the data table's counters
     if (simplified && (rc = vhx::ensure(c, c->build.simp, simp_bytes(nleaf)))) return rc;
     const uint64_t voxels = (uint64_t)g.gx * g.gy * g.gz;
     if (on_device) {
         g.a = grid->albedo;
+        g.d = data;
     } else {
-        if ((rc = vhx::ensure(c, c->build.grid, voxels * 4))) return rc;
+        if ((rc = vhx::ensure(c, c->build.grid, voxels * (data ? 8 : 4)))) return rc;
         VHX_HIP(c, hipMemcpyAsync(c->build.grid.ptr, grid->albedo, voxels * 4, hipMemcpyHostToDevice, c->stream));
         g.a = (const uint32_t *)c->build.grid.ptr;
+        if (data) {  // the data plane follows the albedo plane
+            VHX_HIP(c, hipMemcpyAsync((uint32_t *)c->build.grid.ptr + voxels, data, voxels * 4, hipMemcpyHostToDevice,
+                                      c->stream));
+            g.d = g.a + voxels;
+        }
     }
     fa.g = g;
     u64 *occ = (u64 *)c->build.occ.ptr, *rank = (u64 *)c->build.rank.ptr, *first = (u64 *)c->build.first.ptr;
     BuildCtl *ctl = (BuildCtl *)c->build.ctl.ptr;
     const ColorTable t = table_of(c->build.table.ptr);
+    const ColorTable dt = data ? table_of(c->build.dtable.ptr) : ColorTable{};
     // full reset: leaf masks (the other levels are overwritten), counters, table keys free, first indices at maximum
     VHX_HIP(c, hipMemsetAsync(occ, 0, words * 8, c->stream));
-    VHX_HIP(c, hipMemsetAsync(ctl, 0, sizeof(BuildCtl), c->stream));
+    VHX_HIP(c, hipMemsetAsync(ctl, 0, 2 * sizeof(BuildCtl), c->stream));
     VHX_HIP(c, hipMemsetAsync(t.keys, 0, TAB_KEYS_BYTES, c->stream));
     VHX_HIP(c, hipMemsetAsync(t.vals, 0xFF, TAB_VALS_BYTES, c->stream));
+    if (data) {
+        VHX_HIP(c, hipMemsetAsync(dt.keys, 0, TAB_KEYS_BYTES, c->stream));
+        VHX_HIP(c, hipMemsetAsync(dt.vals, 0xFF, TAB_VALS_BYTES, c->stream));
+    }
     const SimpTable sp = simplified ? simp_of(c->build.simp.ptr, nleaf) : SimpTable{};
     if (simplified) {  // absent leaves have no bricks; no colour has a Solid entry yet
         VHX_HIP(c, hipMemsetAsync(sp.pmask, 0, nleaf * 16, c->stream));
@@ -560,17 +629,21 @@ int build_tree(vhx_ctx *c, const vhx_dense_desc *grid, int on_device, bool simpl
 
     // pass A
     {
-        const bool vec = (g.gx % 4u) == 0 && ((uintptr_t)g.a % 16u) == 0;
+        const bool vec = (g.gx % 4u) == 0 && ((uintptr_t)g.a % 16u) == 0 && ((uintptr_t)g.d % 16u) == 0;
         const uint32_t gxv = vec ? g.gx / 4 : g.gx;
         uint32_t xsh = 0;
         while (xsh < 8 && (1u << xsh) < gxv) ++xsh;
         const uint32_t tpr = 1u << xsh, rpb = 256u >> xsh;
         const dim3 blocks((gxv + tpr - 1) / tpr, std::min<uint32_t>((g.gy + rpb * SCAN_ROWS - 1) / (rpb * SCAN_ROWS), 65535u),
                           std::min<uint32_t>(g.gz, 65535u));
-        if (vec)
-            k_dense_scan<4><<<blocks, 256, 0, c->stream>>>(g, xsh, occ + fa.level_off[D], t, ctl);
+        if (data && vec)
+            k_dense_scan<4, 1><<<blocks, 256, 0, c->stream>>>(g, xsh, occ + fa.level_off[D], t, dt, ctl);
+        else if (data)
+            k_dense_scan<1, 1><<<blocks, 256, 0, c->stream>>>(g, xsh, occ + fa.level_off[D], t, dt, ctl);
+        else if (vec)
+            k_dense_scan<4, 0><<<blocks, 256, 0, c->stream>>>(g, xsh, occ + fa.level_off[D], t, dt, ctl);
         else
-            k_dense_scan<1><<<blocks, 256, 0, c->stream>>>(g, xsh, occ + fa.level_off[D], t, ctl);
+            k_dense_scan<1, 0><<<blocks, 256, 0, c->stream>>>(g, xsh, occ + fa.level_off[D], t, dt, ctl);
         VHX_HIP(c, hipGetLastError());
     }
     // occupancy upwards, ranks per level, first brick of every leaf
@@ -587,6 +660,10 @@ int build_tree(vhx_ctx *c, const vhx_dense_desc *grid, int on_device, bool simpl
     // palette
     k_pal_compact<<<TAB_SLOTS / 256, 256, 0, c->stream>>>(t, ctl);
     k_pal_rank<<<PAL_CAP / 256, 256, 0, c->stream>>>(t, ctl);
+    if (data) {  // the data palette, ranked on its own
+        k_pal_compact<<<TAB_SLOTS / 256, 256, 0, c->stream>>>(dt, ctl + 1);
+        k_pal_rank<<<PAL_CAP / 256, 256, 0, c->stream>>>(dt, ctl + 1);
+    }
     VHX_HIP(c, hipGetLastError());
     if (simplified) {  // leaf classes, the first brick of every leaf from its Parted bricks, the solid values
         k_classify<<<(unsigned)std::min<uint64_t>(nleaf, (uint64_t)c->cus * 16), 256, 0, c->stream>>>(
@@ -598,11 +675,14 @@ int build_tree(vhx_ctx *c, const vhx_dense_desc *grid, int on_device, bool simpl
     }
 
     // the one readback before allocation
-    BuildCtl h;
-    VHX_HIP(c, hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    BuildCtl hb[2];
+    VHX_HIP(c, hipMemcpyAsync(hb, ctl, sizeof(hb), hipMemcpyDeviceToHost, c->stream));
     VHX_HIP(c, hipStreamSynchronize(c->stream));
+    const BuildCtl &h = hb[0];
     if (h.overflow || h.ncolors > MAX_COLORS)
         return fail_in(VHX_E_CAPACITY, ": more than 65535 distinct colours");
+    if (hb[1].overflow || hb[1].ncolors > MAX_COLORS)
+        return fail_in(VHX_E_CAPACITY, ": more than 65535 distinct data values");
     if (h.brick_total >= 0x80000000ull) return fail_in(VHX_E_CAPACITY, ": 2^31 bricks or more");
     uint64_t nodes = 0;
     for (uint32_t lv = 0; lv < levels; ++lv) {
@@ -611,6 +691,7 @@ int build_tree(vhx_ctx *c, const vhx_dense_desc *grid, int on_device, bool simpl
     }
     if (nodes >= 0xFFFFFFFFull) return fail_in(VHX_E_CAPACITY, ": 2^32 nodes or more");
     fa.color_count = h.ncolors;
+    fa.data_count = hb[1].ncolors;
     fa.solid_count = simplified ? h.solid_count : 0u;
     vhx_tree_desc counts{};
     counts.boxtree_size = S;
@@ -619,6 +700,7 @@ int build_tree(vhx_ctx *c, const vhx_dense_desc *grid, int on_device, bool simpl
     counts.brick_count = (uint32_t)h.brick_total;
     counts.solid_count = fa.solid_count;
     counts.color_count = h.ncolors;
+    counts.data_count = hb[1].ncolors;
     return vhx::receive_tree(c, counts, fill_from_scratch, &fa);
 }
 
@@ -627,11 +709,16 @@ int build_tree(vhx_ctx *c, const vhx_dense_desc *grid, int on_device, bool simpl
 extern "C" {
 
 int vhx_build_tree_dense(vhx_ctx *c, const vhx_dense_desc *grid, int on_device) {
-    return build_tree(c, grid, on_device, false, "vhx_build_tree_dense");
+    return build_tree(c, grid, nullptr, on_device, false, "vhx_build_tree_dense");
 }
 
 int vhx_build_tree_dense_simplified(vhx_ctx *c, const vhx_dense_desc *grid, int on_device) {
-    return build_tree(c, grid, on_device, true, "vhx_build_tree_dense_simplified");
+    return build_tree(c, grid, nullptr, on_device, true, "vhx_build_tree_dense_simplified");
+}
+
+int vhx_build_tree_dense_data(vhx_ctx *c, const vhx_dense_desc *grid, const uint32_t *data, int on_device) {
+    if (!data) return vhx_build_tree_dense(c, grid, on_device);
+    return build_tree(c, grid, data, on_device, false, "vhx_build_tree_dense_data");
 }
 
 int vhx_tree_counts(const vhx_ctx *c, vhx_tree_desc *counts) {

@@ -231,7 +231,7 @@ void vhx_destroy(vhx_ctx *c) {
                       &c->flags, &c->qargs, &c->state, &c->stateq, &c->upd, &c->prepass_depth, &c->batch_args, &c->scan_part,
                       &c->shadow_args, &c->tail_list[0], &c->tail_list[1], &c->tail_mask, &c->build.occ, &c->build.rank,
                       &c->build.first, &c->build.part, &c->build.table, &c->build.ctl, &c->build.grid,
-                      &c->build.simp, &c->work, &c->query, &c->edit.oldn, &c->edit.aft, &c->edit.need,
+                      &c->build.simp, &c->build.dtable, &c->work, &c->query, &c->edit.oldn, &c->edit.aft, &c->edit.need,
                       &c->edit.rank, &c->edit.nmask, &c->edit.first, &c->edit.ctl, &c->compact.new_of,
                       &c->compact.old_of, &c->compact.nmask, &c->compact.nrank, &c->compact.bmask,
                       &c->compact.bfirst, &c->compact.bnew, &c->compact.bsrc, &c->compact.ctl, &c->simplify.binfo,

@@ -21,6 +21,10 @@
 //                           reads the old leaf types)
 //            k_edit_nodes   types, occupancy, headers, entries and child records of the lattice nodes, per level
 //
+// vhx_write_dense_data runs the same passes with DATA = 1: a box voxel is an entry where it has a
+// colour or a data value, the data values have a table of their own (build.dtable, seeded from data_palette, entries
+// equal to 0 skipped) with the colours' compact / rank / shift triple, and the emission writes both halves.
+//
 // The emission writes the derived state of what it writes (headers, bitmaps of written bricks, child records of written
 // entries) itself: a bitmap is the ballot the leaf pass already needs to decide whether the brick exists. Every global
 // write is a plain store; the atomics are ORs, minima, table claims and counts, as in vhx_build.hip, so the image does
@@ -43,6 +47,7 @@ struct EditCtl {
     uint32_t bad;  // the tree under the box is not of canonical depth
     uint32_t orphan_nodes, orphan_bricks;
     uint32_t pad;
+    BuildCtl d;  // vhx_write_dense_data: the data table's ncolors (starts at data_count), overflow and ncompact
 };
 
 struct Lattice {
@@ -53,6 +58,8 @@ struct Lattice {
 struct EditP {
     uint32_t ox, oy, oz, gx, gy, gz, mode, fill;
     const uint32_t *grid;  // null: every voxel of the box is `fill`
+    const uint32_t *dgrid;  // vhx_write_dense_data: the box's data plane; null: every voxel's data value is `dfill`
+    uint32_t dfill;
     uint32_t lg_size, lg_bd, D;
     uint64_t total;  // cells of all levels
     Lattice lv[MAX_LEVELS];
@@ -127,12 +134,15 @@ __global__ __launch_bounds__(256) void k_edit_walk(EditP p, TreeP t, Scratch s, 
     if (bad) atomicOr(&ctl->bad, 1u);
 }
 
+// DATA = 1 seeds the data table from data_palette: an entry equal to 0 is skipped (0 is the free key, and a written data
+// value is never 0)
+template <int DATA>
 __global__ __launch_bounds__(256) void k_edit_seed(ColorTable t, const uint32_t *pal, uint32_t n, EditCtl *ctl) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i == 0) ctl->b.ncolors = n;  // the leaf pass counts the claims of new colours on top
+    if (i == 0) (DATA ? ctl->d : ctl->b).ncolors = n;  // the leaf pass counts the claims of new values on top
     if (i >= n) return;
     const uint32_t c = pal[i];
-    if ((c >> 24) == 0) return;  // never looked up: a written voxel's colour has a non-zero alpha byte
+    if (DATA ? c == 0 : (c >> 24) == 0) return;  // never looked up: a written voxel's colour has a non-zero alpha byte
     uint32_t h = color_hash(c);
     for (uint32_t probe = 0; probe < TAB_SLOTS; ++probe, h = (h + 1) & TAB_MASK) {
         uint32_t k = t.keys[h];
@@ -150,15 +160,18 @@ __global__ __launch_bounds__(256) void k_edit_seed(ColorTable t, const uint32_t 
 // The touched leaves. EMIT = 0 analyses (reads the tree only), EMIT = 1 writes; both derive a brick's bitmap after the
 // write the same way, so the second pass reproduces what the first one counted. Loop bounds are wave uniform: the
 // ballots run with all 64 lanes.
-template <int EMIT>
-__global__ __launch_bounds__(256) void k_edit_leaf(EditP p, TreeP t, Scratch s, ColorTable tab, EditCtl *ctl) {
+// DATA = 1 (vhx_write_dense_data): a box voxel is an entry where it has a colour or a data value, its data values go
+// into `dtab`, and the emission writes both halves.
+template <int EMIT, int DATA>
+__global__ __launch_bounds__(256) void k_edit_leaf(EditP p, TreeP t, Scratch s, ColorTable tab, ColorTable dtab,
+                                                   EditCtl *ctl) {
     __shared__ uint32_t s_ty, s_u, s_orph;
     __shared__ u64 s_aft, s_nm;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const Lattice &L = p.lv[p.D];
     const uint64_t nleaf = (uint64_t)L.n[0] * L.n[1] * L.n[2];
     const uint32_t bd = 1u << p.lg_bd, n3 = 1u << (3u * p.lg_bd), lsh = p.lg_bd + 2u;
-    uint32_t last_c = 0, last_v = VHX_EMPTY;
+    uint32_t last_c = 0, last_d = 0, last_v = VHX_EMPTY;
     for (uint64_t cell = blockIdx.x; cell < nleaf; cell += gridDim.x) {
         const uint32_t node = s.oldn[L.off + cell];
         const u64 aft = EMIT ? s.aft[L.off + cell] : 0ull;
@@ -224,9 +237,11 @@ __global__ __launch_bounds__(256) void k_edit_leaf(EditP p, TreeP t, Scratch s, 
                 const uint32_t vx = bx + cx, vy = by + cy, vz = bz + cz;
                 const uint32_t rx = vx - p.ox, ry = vy - p.oy, rz = vz - p.oz;
                 const bool inbox = valid && rx < p.gx && ry < p.gy && rz < p.gz;
-                uint32_t g = 0;
+                uint32_t g = 0, gd = 0;
                 if (inbox) g = p.grid ? p.grid[((uint64_t)rz * p.gy + ry) * p.gx + rx] : p.fill;
-                const bool vis = (g >> 24) != 0;
+                if (DATA && inbox) gd = p.dgrid ? p.dgrid[((uint64_t)rz * p.gy + ry) * p.gx + rx] : p.dfill;
+                const bool col = (g >> 24) != 0;  // the voxel has a colour
+                const bool vis = col || (DATA && gd != 0);  // the box's voxel is an entry
                 const bool covered = inbox && (p.mode == VHX_WRITE_REPLACE || vis);
                 uint32_t raw = VHX_EMPTY;
                 bool ne = false;
@@ -248,20 +263,31 @@ __global__ __launch_bounds__(256) void k_edit_leaf(EditP p, TreeP t, Scratch s, 
                 if (!EMIT) {
                     {  // a voxel whose left neighbour in its row holds its colour has the larger index; a fill's
                        // one colour is recorded by the box's first voxel
-                        const bool cand = covered && vis && (p.grid || (rx | ry | rz) == 0u);
+                        const bool cand = covered && col && (p.grid || (rx | ry | rz) == 0u);
                         const uint32_t pg = __shfl_up(g, 1);
                         const bool pc = __shfl_up((int)cand, 1) != 0;
                         if (cand && !(lane > 0 && cx > 0 && pc && pg == g))
                             color_insert(tab, &ctl->b, g, NEW_BASE + ((u64)rx * p.gy + ry) * p.gz + rz);
+                    }
+                    if (DATA) {  // the data values, the same way
+                        const bool cand = covered && gd != 0 && (p.dgrid || (rx | ry | rz) == 0u);
+                        const uint32_t pg = __shfl_up(gd, 1);
+                        const bool pc = __shfl_up((int)cand, 1) != 0;
+                        if (cand && !(lane > 0 && cx > 0 && pc && pg == gd))
+                            color_insert(dtab, &ctl->d, gd, NEW_BASE + ((u64)rx * p.gy + ry) * p.gz + rz);
                     }
                 } else {
                     const uint64_t va = ((uint64_t)slot << (3u * p.lg_bd)) + c;
                     if (covered) {
                         uint32_t v = VHX_EMPTY;
                         if (vis) {
-                            if (g != last_c) {
-                                last_c = g;
-                                last_v = color_lookup(tab, g) | 0xFFFF0000u;  // pix_visual: colour index, no data
+                            const uint32_t gc = col ? g : 0u;
+                            if (gc != last_c || gd != last_d) {
+                                last_c = gc;
+                                last_d = gd;
+                                // pix_visual, pix_informative, pix_complex: 0xFFFF for the half that is none
+                                last_v = (gc ? color_lookup(tab, gc) : 0xFFFFu) |
+                                         ((gd ? color_lookup(dtab, gd) : 0xFFFFu) << 16);
                             }
                             v = last_v;
                         }
@@ -327,13 +353,13 @@ __global__ __launch_bounds__(256) void k_edit_reduce(EditP p, TreeP t, Scratch s
     if (m == 0 && node != NONE && lv != 0) atomicAdd(&ctl->orphan_nodes, 1u);
 }
 
-// the new colours of the table (first index at or above NEW_BASE), compacted for k_pal_rank
-__global__ __launch_bounds__(256) void k_edit_pal_compact(ColorTable t, EditCtl *ctl) {
+// the new colours of the table (first index at or above NEW_BASE), compacted for k_pal_rank; `b` is the table's counters
+__global__ __launch_bounds__(256) void k_edit_pal_compact(ColorTable t, BuildCtl *b) {
     const uint32_t h = blockIdx.x * 256 + threadIdx.x;
     if (h >= TAB_SLOTS) return;
     const uint32_t k = t.keys[h];
     if (k == 0 || t.vals[h] < NEW_BASE) return;
-    const uint32_t pos = atomicAdd(&ctl->b.ncompact, 1u);  // any order: the ranks come from the first indices
+    const uint32_t pos = atomicAdd(&b->ncompact, 1u);  // any order: the ranks come from the first indices
     if (pos >= PAL_CAP) return;
     t.ckey[pos] = k;
     t.cidx[pos] = t.vals[h];
@@ -341,9 +367,9 @@ __global__ __launch_bounds__(256) void k_edit_pal_compact(ColorTable t, EditCtl 
 }
 
 // k_pal_rank left each new colour's rank among the new ones in its slot: its palette index is color_count further
-__global__ __launch_bounds__(256) void k_edit_pal_shift(ColorTable t, const EditCtl *ctl, uint32_t color_count) {
+__global__ __launch_bounds__(256) void k_edit_pal_shift(ColorTable t, const BuildCtl *b, uint32_t color_count) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= min(ctl->b.ncompact, PAL_CAP)) return;
+    if (i >= min(b->ncompact, PAL_CAP)) return;
     t.vals[t.cslot[i]] += color_count;
 }
 
@@ -406,11 +432,9 @@ TreeP tree_of(const vhx_ctx *c, const vhx_tree_desc &d) {
     return t;
 }
 
-}  // namespace
-
-extern "C" {
-
-int vhx_write_dense(vhx_ctx *c, const vhx_dense_in *box, int on_device) {
+// both dense writes: `with_data` is vhx_write_dense_data with a data plane or a data fill
+int write_dense(vhx_ctx *c, const vhx_dense_in *box, const uint32_t *data, uint32_t fill_data, bool with_data,
+                int on_device) {
     if (!c || !box) return fail(c, VHX_E_INVALID_ARG, "vhx_write_dense: null argument");
     if (c->shared) return fail(c, VHX_E_STATE, "vhx_write_dense on a shared context: write through the owner");
     if (!c->tree->uploaded) return fail(c, VHX_E_STATE, "vhx_write_dense before vhx_upload_tree");
@@ -427,6 +451,7 @@ int vhx_write_dense(vhx_ctx *c, const vhx_dense_in *box, int on_device) {
     p.gx = box->gx, p.gy = box->gy, p.gz = box->gz;
     p.mode = box->mode;
     p.fill = box->fill;
+    p.dfill = fill_data;
     while ((1u << p.lg_size) < d.boxtree_size) ++p.lg_size;
     while ((1u << p.lg_bd) < d.brick_dim) ++p.lg_bd;
     if ((1u << p.lg_size) != d.boxtree_size || (1u << p.lg_bd) != d.brick_dim || p.lg_size < p.lg_bd + 2u ||
@@ -466,28 +491,47 @@ int vhx_write_dense(vhx_ctx *c, const vhx_dense_in *box, int on_device) {
     if ((rc = vhx::ensure(c, c->edit.ctl, sizeof(EditCtl)))) return rc;
     if ((rc = vhx::ensure(c, c->build.part, ((cells_max + SCAN_TILE - 1) / SCAN_TILE) * 8))) return rc;
     if ((rc = vhx::ensure(c, c->build.table, TAB_BYTES))) return rc;
-    if (box->albedo && !on_device) {
+    if (with_data && (rc = vhx::ensure(c, c->build.dtable, TAB_BYTES))) return rc;
+    p.grid = box->albedo;
+    p.dgrid = data;
+    if ((box->albedo || data) && !on_device) {  // host planes: the data plane follows the albedo plane
         const uint64_t bytes = (uint64_t)p.gx * p.gy * p.gz * 4;
-        if ((rc = vhx::ensure(c, c->build.grid, bytes))) return rc;
-        VHX_HIP(c, hipMemcpyAsync(c->build.grid.ptr, box->albedo, bytes, hipMemcpyHostToDevice, c->stream));
-        p.grid = (const uint32_t *)c->build.grid.ptr;
-    } else {
-        p.grid = box->albedo;
+        if ((rc = vhx::ensure(c, c->build.grid, bytes * ((box->albedo ? 1u : 0u) + (data ? 1u : 0u))))) return rc;
+        char *at = (char *)c->build.grid.ptr;
+        if (box->albedo) {
+            VHX_HIP(c, hipMemcpyAsync(at, box->albedo, bytes, hipMemcpyHostToDevice, c->stream));
+            p.grid = (const uint32_t *)at;
+            at += bytes;
+        }
+        if (data) {
+            VHX_HIP(c, hipMemcpyAsync(at, data, bytes, hipMemcpyHostToDevice, c->stream));
+            p.dgrid = (const uint32_t *)at;
+        }
     }
     Scratch s{(uint32_t *)c->edit.oldn.ptr, (u64 *)c->edit.aft.ptr,   (u64 *)c->edit.need.ptr,
               (u64 *)c->edit.rank.ptr,      (u64 *)c->edit.nmask.ptr, (u64 *)c->edit.first.ptr};
     EditCtl *ctl = (EditCtl *)c->edit.ctl.ptr;
     const ColorTable tab = table_of(c->build.table.ptr);
+    const ColorTable dtab = with_data ? table_of(c->build.dtable.ptr) : ColorTable{};
     TreeP t = tree_of(c, d);
     // reset: counters, table keys free, first indices at maximum (every scratch word is written before it is read)
     VHX_HIP(c, hipMemsetAsync(ctl, 0, sizeof(EditCtl), c->stream));
     VHX_HIP(c, hipMemsetAsync(tab.keys, 0, TAB_KEYS_BYTES, c->stream));
     VHX_HIP(c, hipMemsetAsync(tab.vals, 0xFF, TAB_VALS_BYTES, c->stream));
+    if (with_data) {
+        VHX_HIP(c, hipMemsetAsync(dtab.keys, 0, TAB_KEYS_BYTES, c->stream));
+        VHX_HIP(c, hipMemsetAsync(dtab.vals, 0xFF, TAB_VALS_BYTES, c->stream));
+    }
 
     k_edit_walk<<<blocks_for(p.total), 256, 0, c->stream>>>(p, t, s, ctl);
-    k_edit_seed<<<blocks_for((uint64_t)d.color_count + 1), 256, 0, c->stream>>>(tab, t.color, d.color_count, ctl);
+    k_edit_seed<0><<<blocks_for((uint64_t)d.color_count + 1), 256, 0, c->stream>>>(tab, t.color, d.color_count, ctl);
+    if (with_data)
+        k_edit_seed<1><<<blocks_for((uint64_t)d.data_count + 1), 256, 0, c->stream>>>(dtab, t.data, d.data_count, ctl);
     const unsigned leaf_blocks = (unsigned)std::min<uint64_t>(nleaf, (uint64_t)c->cus * 32);
-    k_edit_leaf<0><<<leaf_blocks, 256, 0, c->stream>>>(p, t, s, tab, ctl);
+    if (with_data)
+        k_edit_leaf<0, 1><<<leaf_blocks, 256, 0, c->stream>>>(p, t, s, tab, dtab, ctl);
+    else
+        k_edit_leaf<0, 0><<<leaf_blocks, 256, 0, c->stream>>>(p, t, s, tab, dtab, ctl);
     for (uint32_t lv = p.D; lv-- > 0;) {
         const Lattice &L = p.lv[lv];
         k_edit_reduce<<<blocks_for((uint64_t)L.n[0] * L.n[1] * L.n[2]), 256, 0, c->stream>>>(p, t, s, lv, ctl);
@@ -500,9 +544,14 @@ int vhx_write_dense(vhx_ctx *c, const vhx_dense_in *box, int on_device) {
             return rc;
     }
     if ((rc = scan_level<1>(c, s.nmask, nleaf, false, s.first, &ctl->b.brick_total))) return rc;
-    k_edit_pal_compact<<<TAB_SLOTS / 256, 256, 0, c->stream>>>(tab, ctl);
+    k_edit_pal_compact<<<TAB_SLOTS / 256, 256, 0, c->stream>>>(tab, &ctl->b);
     k_pal_rank<<<PAL_CAP / 256, 256, 0, c->stream>>>(tab, &ctl->b);
-    k_edit_pal_shift<<<PAL_CAP / 256, 256, 0, c->stream>>>(tab, ctl, d.color_count);
+    k_edit_pal_shift<<<PAL_CAP / 256, 256, 0, c->stream>>>(tab, &ctl->b, d.color_count);
+    if (with_data) {  // the new data values, ranked on their own after data_count
+        k_edit_pal_compact<<<TAB_SLOTS / 256, 256, 0, c->stream>>>(dtab, &ctl->d);
+        k_pal_rank<<<PAL_CAP / 256, 256, 0, c->stream>>>(dtab, &ctl->d);
+        k_edit_pal_shift<<<PAL_CAP / 256, 256, 0, c->stream>>>(dtab, &ctl->d, d.data_count);
+    }
     VHX_HIP(c, hipGetLastError());
 
     // the one readback; the tree has only been read so far
@@ -514,6 +563,8 @@ int vhx_write_dense(vhx_ctx *c, const vhx_dense_in *box, int on_device) {
                                     "streamed view)");
     if (h.b.overflow || h.b.ncolors > MAX_COLORS)
         return fail(c, VHX_E_CAPACITY, "vhx_write_dense: more than 65535 colours");
+    if (with_data && (h.d.overflow || h.d.ncolors > MAX_COLORS))
+        return fail(c, VHX_E_CAPACITY, "vhx_write_dense_data: more than 65535 data values");
     if ((uint64_t)d.brick_count + h.b.brick_total >= 0x80000000ull)
         return fail(c, VHX_E_CAPACITY, "vhx_write_dense: 2^31 bricks or more");
     uint64_t nodes = d.node_count;
@@ -526,10 +577,14 @@ int vhx_write_dense(vhx_ctx *c, const vhx_dense_in *box, int on_device) {
     nd.node_count = (uint32_t)nodes;
     nd.brick_count = d.brick_count + (uint32_t)h.b.brick_total;
     nd.color_count = h.b.ncolors;
+    if (with_data) nd.data_count = h.d.ncolors;
     if ((rc = vhx::grow_tree(c, &nd))) return rc;
     t = tree_of(c, d);  // the buffers may have moved; the counts stay the old ones
 
-    k_edit_leaf<1><<<leaf_blocks, 256, 0, c->stream>>>(p, t, s, tab, ctl);
+    if (with_data)
+        k_edit_leaf<1, 1><<<leaf_blocks, 256, 0, c->stream>>>(p, t, s, tab, dtab, ctl);
+    else
+        k_edit_leaf<1, 0><<<leaf_blocks, 256, 0, c->stream>>>(p, t, s, tab, dtab, ctl);
     for (uint32_t lv = 0; lv <= p.D; ++lv) {
         const Lattice &L = p.lv[lv];
         k_edit_nodes<<<blocks_for((uint64_t)L.n[0] * L.n[1] * L.n[2] * 64), 256, 0, c->stream>>>(p, t, s, lv);
@@ -538,11 +593,26 @@ int vhx_write_dense(vhx_ctx *c, const vhx_dense_in *box, int on_device) {
     if (nd.color_count > d.color_count)
         VHX_HIP(c, hipMemcpyAsync((uint32_t *)c->tree->raw[VHX_BUF_COLOR_PALETTE].ptr + d.color_count, tab.pal,
                                   (uint64_t)(nd.color_count - d.color_count) * 4, hipMemcpyDeviceToDevice, c->stream));
+    if (nd.data_count > d.data_count)
+        VHX_HIP(c, hipMemcpyAsync((uint32_t *)c->tree->raw[VHX_BUF_DATA_PALETTE].ptr + d.data_count, dtab.pal,
+                                  (uint64_t)(nd.data_count - d.data_count) * 4, hipMemcpyDeviceToDevice, c->stream));
     VHX_HIP(c, hipStreamSynchronize(c->stream));
     c->tree->desc = nd;
     c->tree->orphan_nodes += h.orphan_nodes;
     c->tree->orphan_bricks += h.orphan_bricks;
     return ws.end();  // the next trace of every context of the tree waits for this write
+}
+
+}  // namespace
+
+extern "C" {
+
+int vhx_write_dense(vhx_ctx *c, const vhx_dense_in *box, int on_device) {
+    return write_dense(c, box, nullptr, 0u, false, on_device);
+}
+
+int vhx_write_dense_data(vhx_ctx *c, const vhx_dense_in *box, const uint32_t *data, uint32_t fill_data, int on_device) {
+    return write_dense(c, box, data, fill_data, data != nullptr || fill_data != 0u, on_device);
 }
 
 }  // extern "C"

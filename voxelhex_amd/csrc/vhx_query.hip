@@ -3,7 +3,8 @@
 // Kernels
 //   k_get_voxels     BoxTree::get (src/boxtree/mod.rs:223-317) for a batch of positions, one lane per position
 //   k_read_dense     a box of the tree as a dense albedo grid, tree driven: one workgroup per aligned cube of voxels
-// Host side: vhx_get_voxels, vhx_read_dense. Both are ordered like a trace (TraceScope) and launch no kernel of another
+//                    (DATA: and as a dense grid of data values, in the same walk -- vhx_read_dense_data)
+// Host side: vhx_get_voxels, vhx_read_dense, vhx_read_dense_data. All are ordered like a trace (TraceScope) and launch no kernel of another
 // unit except through refresh_child_rec. Wave-uniform loads and the sectant of a position come from treewalk.hpp.
 //
 // The walk runs in integers (DESIGN.md §8.6 argues why that equals the reference's f32 sectant_for / matrix_index_for):
@@ -110,12 +111,26 @@ __global__ void __launch_bounds__(256) k_get_voxels(DevTree t, QShape q, const u
 
 struct DenseBox {
     uint32_t ox, oy, oz, gx, gy, gz;
-    uint32_t *out;
+    uint32_t *out;           // vhx_read_dense_data: may be null (data only)
+    uint32_t *dout;          // vhx_read_dense_data: the data plane
+    const uint32_t *dpal;    // the tree's data_palette
+    uint32_t dcount;
     uint32_t lgu;            // log2 of the work unit's edge U
     uint32_t ux0, uy0, uz0;  // first unit of the box per axis (in units)
     uint32_t nux, nuy, nuz;  // units per axis
-    uint32_t vec;            // rows of the output start and end on 16-byte boundaries
+    uint32_t vec;            // rows of the output (of both planes) start and end on 16-byte boundaries
 };
+
+// the data value vhx_read_dense_data writes for a value: the palette entry of its data index unless the value is
+// VHX_EMPTY or the index none or out of the palette
+__device__ __forceinline__ uint32_t data_of(const DenseBox &b, uint32_t v) {
+    const uint32_t di = v >> 16;
+    if (v == VHX_EMPTY || di == 0xFFFFu || di >= b.dcount) return 0u;
+    return b.dpal[di];
+}
+__device__ __forceinline__ uint4 data_of(const DenseBox &b, uint4 v) {
+    return make_uint4(data_of(b, v.x), data_of(b, v.y), data_of(b, v.z), data_of(b, v.w));
+}
 
 // How a work unit is filled, chosen once per unit from its wave-uniform descent
 enum : uint32_t {
@@ -129,10 +144,14 @@ enum : uint32_t {
 // min(brick_dim, 16) above (a brick, or a 16^3 part of one): at most 4096 voxels, and never cut by a node or brick
 // boundary except, at brick_dim <= 4, by the bricks of the one leaf it is. The workgroup walks to the unit's node once,
 // turns the unit into output colours in LDS (constant fills skip that) and writes the part inside the box as rows.
-template <bool REC>
+// DATA: the same walk fills a second tile with the unit's data values and writes the data plane beside the albedo plane
+// (which may then be absent).
+template <bool REC, bool DATA>
 __global__ void __launch_bounds__(256) k_read_dense(DevTree t, QShape q, DenseBox b, uint64_t nunits) {
-    __shared__ uint4 tile4[1024];
+    __shared__ uint4 tile4[DATA ? 2048 : 1024];
     uint32_t *tile = (uint32_t *)tile4;
+    uint4 *dtile4 = tile4 + (DATA ? 1024 : 0);
+    uint32_t *dtile = (uint32_t *)dtile4;
     const uint32_t lgu = b.lgu, U = 1u << lgu, um = U - 1u;
     const uint32_t nvox = 1u << (3u * lgu);
     for (uint64_t u = blockIdx.x; u < nunits; u += gridDim.x) {
@@ -153,13 +172,17 @@ __global__ void __launch_bounds__(256) k_read_dense(DevTree t, QShape q, DenseBo
             lg -= 2u;
         }
         const bool uniform = type == VHX_NODE_UNIFORM_LEAF, leaf = type == VHX_NODE_LEAF;
-        uint32_t mode = FILL_CONST, fill = 0u, desc = VHX_EMPTY;
+        uint32_t mode = FILL_CONST, fill = 0u, dfill = 0u, desc = VHX_EMPTY;
         if (uniform || (leaf && lg - 2u >= lgu)) {  // one brick for the whole unit
             desc = (!REC && uniform) ? __builtin_amdgcn_readfirstlane(uload(&t.children[(uint64_t)node * 64u])) : entry;
             if (desc == VHX_EMPTY) {
             } else if (desc & VHX_SOLID_BIT) {
                 const uint32_t i = desc & 0x7FFFFFFFu;
-                if (i < q.solid_count) fill = __builtin_amdgcn_readfirstlane(albedo_of(t, uload(&t.solid[i])));
+                if (i < q.solid_count) {
+                    const uint32_t sv = uload(&t.solid[i]);
+                    fill = __builtin_amdgcn_readfirstlane(albedo_of(t, sv));
+                    if (DATA) dfill = __builtin_amdgcn_readfirstlane(data_of(b, sv));
+                }
             } else if (desc < q.brick_count) {
                 mode = (!uniform && lg - 2u == q.lg_bd && q.lg_bd >= 3u) ? FILL_ROWS : FILL_CELLS;
             }
@@ -174,23 +197,33 @@ __global__ void __launch_bounds__(256) k_read_dense(DevTree t, QShape q, DenseBo
                 const uint32_t qx = i & (U / 4u - 1u), cy = (i >> (lgu - 2u)) & um, cz = i >> (2u * lgu - 2u);
                 const uint32_t sx = (X & bm) + 4u * qx, sy = (Y & bm) + cy, sz = (Z & bm) + cz;
                 const uint32_t src = (((sz << q.lg_bd) + sy) << q.lg_bd) + sx;
-                tile4[i] = albedo_of(t, *(const uint4 *)(brick + src));
+                const uint4 raw = *(const uint4 *)(brick + src);
+                tile4[i] = albedo_of(t, raw);
+                if (DATA) dtile4[i] = data_of(b, raw);
             }
         } else if (mode == FILL_LEAF4) {
             for (uint32_t i = threadIdx.x; i < 1024u; i += 256u) {
                 const uint32_t s = i >> 4, r = i & 15u;  // brick, and its row (y, z)
                 const uint32_t d = t.children[(uint64_t)node * 64u + s];
-                uint4 c = make_uint4(0u, 0u, 0u, 0u);
+                uint4 c = make_uint4(0u, 0u, 0u, 0u), dv = c;
                 if (d == VHX_EMPTY) {
                 } else if (d & VHX_SOLID_BIT) {
                     const uint32_t k = d & 0x7FFFFFFFu;
-                    const uint32_t a = k < q.solid_count ? albedo_of(t, t.solid[k]) : 0u;
+                    const uint32_t sv = k < q.solid_count ? t.solid[k] : VHX_EMPTY;
+                    const uint32_t a = albedo_of(t, sv);
                     c = make_uint4(a, a, a, a);
+                    if (DATA) {
+                        const uint32_t e = data_of(b, sv);
+                        dv = make_uint4(e, e, e, e);
+                    }
                 } else if (d < q.brick_count) {
-                    c = albedo_of(t, *(const uint4 *)(t.voxels + (uint64_t)d * 64u + r * 4u));
+                    const uint4 raw = *(const uint4 *)(t.voxels + (uint64_t)d * 64u + r * 4u);
+                    c = albedo_of(t, raw);
+                    if (DATA) dv = data_of(b, raw);
                 }
                 const uint32_t ty = ((s >> 2) & 3u) * 4u + (r & 3u), tz = (s >> 4) * 4u + (r >> 2);
                 tile4[(tz * 16u + ty) * 4u + (s & 3u)] = c;
+                if (DATA) dtile4[(tz * 16u + ty) * 4u + (s & 3u)] = dv;
             }
         } else if (mode == FILL_CELLS) {
             for (uint32_t i = threadIdx.x; i < nvox; i += 256u) {
@@ -205,7 +238,9 @@ __global__ void __launch_bounds__(256) k_read_dense(DevTree t, QShape q, DenseBo
                 } else {
                     e = t.children[at];
                 }
-                tile[i] = albedo_of(t, leaf_value<REC>(t, q, node, type, e, cocc, lg, x, y, z));
+                const uint32_t val = leaf_value<REC>(t, q, node, type, e, cocc, lg, x, y, z);
+                tile[i] = albedo_of(t, val);
+                if (DATA) dtile[i] = data_of(b, val);
             }
         }
         if (mode != FILL_CONST) __syncthreads();
@@ -217,18 +252,34 @@ __global__ void __launch_bounds__(256) k_read_dense(DevTree t, QShape q, DenseBo
                 const uint32_t x = X + 4u * (i & (U / 4u - 1u)) - b.ox, y = Y + ((i >> (lgu - 2u)) & um) - b.oy,
                                z = Z + (i >> (2u * lgu - 2u)) - b.oz;
                 if (x < b.gx && y < b.gy && z < b.gz) {
-                    uint4 v = f4;
-                    if (mode != FILL_CONST) v = tile4[i];
-                    *(uint4 *)(b.out + ((uint64_t)z * b.gy + y) * b.gx + x) = v;
+                    const uint64_t at = ((uint64_t)z * b.gy + y) * b.gx + x;
+                    if (!DATA || b.out) {
+                        uint4 v = f4;
+                        if (mode != FILL_CONST) v = tile4[i];
+                        *(uint4 *)(b.out + at) = v;
+                    }
+                    if (DATA) {
+                        uint4 v = make_uint4(dfill, dfill, dfill, dfill);
+                        if (mode != FILL_CONST) v = dtile4[i];
+                        *(uint4 *)(b.dout + at) = v;
+                    }
                 }
             }
         } else {
             for (uint32_t i = threadIdx.x; i < nvox; i += 256u) {
                 const uint32_t x = X + (i & um) - b.ox, y = Y + ((i >> lgu) & um) - b.oy, z = Z + (i >> (2u * lgu)) - b.oz;
                 if (x < b.gx && y < b.gy && z < b.gz) {
-                    uint32_t v = fill;
-                    if (mode != FILL_CONST) v = tile[i];
-                    b.out[((uint64_t)z * b.gy + y) * b.gx + x] = v;
+                    const uint64_t at = ((uint64_t)z * b.gy + y) * b.gx + x;
+                    if (!DATA || b.out) {
+                        uint32_t v = fill;
+                        if (mode != FILL_CONST) v = tile[i];
+                        b.out[at] = v;
+                    }
+                    if (DATA) {
+                        uint32_t v = dfill;
+                        if (mode != FILL_CONST) v = dtile[i];
+                        b.dout[at] = v;
+                    }
                 }
             }
         }
@@ -284,6 +335,70 @@ bool has_child_rec(const vhx_ctx *c) {
     return bd * bd * bd <= 64;
 }
 
+// both dense reads; `name` is the one called, for the error texts. with_data: `data` receives the data plane and
+// box->albedo may be null.
+int read_dense(vhx_ctx *c, const vhx_dense_out *box, uint32_t *data, bool with_data, int on_device, const char *name) {
+    if (!c || !box) return VHX_E_INVALID_ARG;
+    if (!c->tree->uploaded) return fail(c, VHX_E_STATE, std::string(name) + " before vhx_upload_tree");
+    const uint64_t S = c->tree->desc.boxtree_size;
+    if ((with_data ? !data : !box->albedo) || box->gx == 0 || box->gy == 0 || box->gz == 0 ||
+        (uint64_t)box->ox + box->gx > S || (uint64_t)box->oy + box->gy > S || (uint64_t)box->oz + box->gz > S)
+        return fail(c, VHX_E_INVALID_ARG, std::string(name) + ": a null grid, an extent of 0, or a box outside the root cube");
+    const uint64_t voxels = (uint64_t)box->gx * box->gy * box->gz;
+    if (with_data && on_device && box->albedo) {
+        const char *a0 = (const char *)box->albedo, *d0 = (const char *)data;
+        if (a0 < d0 + voxels * 4 && d0 < a0 + voxels * 4)
+            return fail(c, VHX_E_INVALID_ARG, std::string(name) + ": the data plane overlaps the albedo plane");
+    }
+    VHX_HIP(c, hipSetDevice(c->device));
+    VHX_STREAM(c);
+    TraceScope scope(c);
+    if (scope.rc) return scope.rc;
+    int rc;
+    DenseBox b{};
+    b.ox = box->ox, b.oy = box->oy, b.oz = box->oz;
+    b.gx = box->gx, b.gy = box->gy, b.gz = box->gz;
+    b.out = box->albedo;
+    b.dout = data;
+    if (!on_device) {  // the data plane follows the albedo plane
+        if ((rc = ensure(c, c->query, voxels * (with_data ? 8 : 4)))) return rc;
+        b.out = (!with_data || box->albedo) ? (uint32_t *)c->query.ptr : nullptr;
+        if (with_data) b.dout = (uint32_t *)c->query.ptr + voxels;
+    }
+    DevTree t;
+    QShape q;
+    if ((rc = begin_query(c, name, t, q))) return rc;
+    b.dpal = (const uint32_t *)c->tree->raw[VHX_BUF_DATA_PALETTE].ptr;
+    b.dcount = b.dpal ? c->tree->desc.data_count : 0u;
+    const bool rec = has_child_rec(c);
+    b.lgu = q.lg_bd <= 2u ? q.lg_bd + 2u : std::min(q.lg_bd, 4u);
+    b.ux0 = b.ox >> b.lgu, b.uy0 = b.oy >> b.lgu, b.uz0 = b.oz >> b.lgu;
+    b.nux = ((b.ox + b.gx - 1u) >> b.lgu) - b.ux0 + 1u;
+    b.nuy = ((b.oy + b.gy - 1u) >> b.lgu) - b.uy0 + 1u;
+    b.nuz = ((b.oz + b.gz - 1u) >> b.lgu) - b.uz0 + 1u;
+    b.vec = ((uintptr_t)b.out % 16u) == 0 && ((uintptr_t)b.dout % 16u) == 0 && (b.gx % 4u) == 0 && (b.ox % 4u) == 0;
+    const uint64_t nunits = (uint64_t)b.nux * b.nuy * b.nuz;
+    // a launch holds fewer than 2^32 threads: past 2^23 units the workgroups stride over them
+    const unsigned blocks = (unsigned)std::min<uint64_t>(nunits, 1ull << 23);
+    if (with_data) {
+        if (rec)
+            k_read_dense<true, true><<<blocks, 256, 0, c->stream>>>(t, q, b, nunits);
+        else
+            k_read_dense<false, true><<<blocks, 256, 0, c->stream>>>(t, q, b, nunits);
+    } else if (rec) {
+        k_read_dense<true, false><<<blocks, 256, 0, c->stream>>>(t, q, b, nunits);
+    } else {
+        k_read_dense<false, false><<<blocks, 256, 0, c->stream>>>(t, q, b, nunits);
+    }
+    VHX_HIP(c, hipGetLastError());
+    if (!on_device) {
+        if (b.out) VHX_HIP(c, hipMemcpyAsync(box->albedo, b.out, voxels * 4, hipMemcpyDeviceToHost, c->stream));
+        if (with_data) VHX_HIP(c, hipMemcpyAsync(data, b.dout, voxels * 4, hipMemcpyDeviceToHost, c->stream));
+        VHX_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    return scope.end();
+}
+
 }  // namespace
 
 extern "C" {
@@ -329,49 +444,11 @@ int vhx_get_voxels(vhx_ctx *c, const uint32_t *positions, uint64_t n, uint32_t *
 }
 
 int vhx_read_dense(vhx_ctx *c, const vhx_dense_out *box, int on_device) {
-    if (!c || !box) return VHX_E_INVALID_ARG;
-    if (!c->tree->uploaded) return fail(c, VHX_E_STATE, "vhx_read_dense before vhx_upload_tree");
-    const uint64_t S = c->tree->desc.boxtree_size;
-    if (!box->albedo || box->gx == 0 || box->gy == 0 || box->gz == 0 || (uint64_t)box->ox + box->gx > S ||
-        (uint64_t)box->oy + box->gy > S || (uint64_t)box->oz + box->gz > S)
-        return fail(c, VHX_E_INVALID_ARG, "vhx_read_dense: a null grid, an extent of 0, or a box outside the root cube");
-    VHX_HIP(c, hipSetDevice(c->device));
-    VHX_STREAM(c);
-    TraceScope scope(c);
-    if (scope.rc) return scope.rc;
-    int rc;
-    const uint64_t voxels = (uint64_t)box->gx * box->gy * box->gz;
-    DenseBox b{};
-    b.ox = box->ox, b.oy = box->oy, b.oz = box->oz;
-    b.gx = box->gx, b.gy = box->gy, b.gz = box->gz;
-    b.out = box->albedo;
-    if (!on_device) {
-        if ((rc = ensure(c, c->query, voxels * 4))) return rc;
-        b.out = (uint32_t *)c->query.ptr;
-    }
-    DevTree t;
-    QShape q;
-    if ((rc = begin_query(c, "vhx_read_dense", t, q))) return rc;
-    const bool rec = has_child_rec(c);
-    b.lgu = q.lg_bd <= 2u ? q.lg_bd + 2u : std::min(q.lg_bd, 4u);
-    b.ux0 = b.ox >> b.lgu, b.uy0 = b.oy >> b.lgu, b.uz0 = b.oz >> b.lgu;
-    b.nux = ((b.ox + b.gx - 1u) >> b.lgu) - b.ux0 + 1u;
-    b.nuy = ((b.oy + b.gy - 1u) >> b.lgu) - b.uy0 + 1u;
-    b.nuz = ((b.oz + b.gz - 1u) >> b.lgu) - b.uz0 + 1u;
-    b.vec = ((uintptr_t)b.out % 16u) == 0 && (b.gx % 4u) == 0 && (b.ox % 4u) == 0;
-    const uint64_t nunits = (uint64_t)b.nux * b.nuy * b.nuz;
-    // a launch holds fewer than 2^32 threads: past 2^23 units the workgroups stride over them
-    const unsigned blocks = (unsigned)std::min<uint64_t>(nunits, 1ull << 23);
-    if (rec)
-        k_read_dense<true><<<blocks, 256, 0, c->stream>>>(t, q, b, nunits);
-    else
-        k_read_dense<false><<<blocks, 256, 0, c->stream>>>(t, q, b, nunits);
-    VHX_HIP(c, hipGetLastError());
-    if (!on_device) {
-        VHX_HIP(c, hipMemcpyAsync(box->albedo, b.out, voxels * 4, hipMemcpyDeviceToHost, c->stream));
-        VHX_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    return scope.end();
+    return read_dense(c, box, nullptr, false, on_device, "vhx_read_dense");
+}
+
+int vhx_read_dense_data(vhx_ctx *c, const vhx_dense_out *box, uint32_t *data, int on_device) {
+    return read_dense(c, box, data, true, on_device, "vhx_read_dense_data");
 }
 
 }  // extern "C"

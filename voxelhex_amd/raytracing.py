@@ -243,14 +243,36 @@ class Raytracer:
         self._check(N.lib().vhx_upload_tree(self._h, ctypes.byref(flat.desc)))
         self._tree = flat
 
-    def build_dense(self, grid, size, brick_dim, simplify=False):
+    def _data_plane(self, data, like, what):
+        """The pointer of a data plane that goes with the grid `like` (a device tensor, or the contiguous numpy array a
+        call passes down): the same kind, shape and device, under the same checks. Returns (pointer, keep-alive)."""
+        if hasattr(like, "data_ptr"):
+            if not hasattr(data, "data_ptr"):
+                raise TypeError(f"{what}: the grid is a device tensor, so the data plane must be one")
+            if tuple(data.shape) != tuple(like.shape):
+                raise TypeError(f"{what}: the data plane has shape {tuple(data.shape)}, the grid {tuple(like.shape)}")
+            data = self._device_tensor(data, what)
+            return data.data_ptr(), data
+        if hasattr(data, "data_ptr"):
+            raise TypeError(f"{what}: the grid is a host array, so the data plane must be one")
+        from .boxtree import _dense_data
+        plane = _dense_data(data, like.shape)
+        return plane.ctypes.data, plane
+
+    def build_dense(self, grid, size, brick_dim, simplify=False, data=None):
         """vhx_build_tree_dense: builds the canonical tree of a dense grid on the GPU and makes it this context's tree
         (the image of FlatTree.from_dense + upload, bit for bit); with simplify=True the simplified tree
         (vhx_build_tree_dense_simplified, the image of FlatTree.from_dense(simplify=True)). `grid` has shape (gz, gy, gx) and holds packed albedos
         r | g<<8 | b<<16 | a<<24, alpha 0 = no voxel: a uint32 numpy array (copied to the device first), or a contiguous
         int32 / uint32 torch tensor on this context's device, read in place. The build runs on the context's stream,
         not on torch's: for a tensor, torch's current stream on the device is synchronised before the call, so the
-        work that produced the grid has finished. The call returns when the tree is ready (download() reads it)."""
+        work that produced the grid has finished. The call returns when the tree is ready (download() reads it).
+        `data` (optional) is a plane of user data values, 0 = none, of the same kind, shape and device as `grid`
+        (vhx_build_tree_dense_data, the image of FlatTree.from_dense(data=)): a voxel with a colour and a data value is
+        a Complex entry, one with a data value and alpha 0 an Informative one, and get / a trace return both palette
+        indices. With `data` and simplify=True the call is the data build followed by self.simplify(), which gives the
+        image of FlatTree.from_dense(data=, simplify=True); unlike the colour-only simplified build, which leaves the
+        previous tree where it fails, a failure of that second step leaves the new, plain tree."""
         if hasattr(grid, "data_ptr"):
             import torch
             if not grid.is_cuda or grid.device.index != self.device:
@@ -267,12 +289,19 @@ class Raytracer:
             from .boxtree import _dense_desc
             d, grid = _dense_desc(grid, size, brick_dim)
             on_device = 0
-        build = N.lib().vhx_build_tree_dense_simplified if simplify else N.lib().vhx_build_tree_dense
-        rc = build(self._h, ctypes.byref(d), on_device)
+        if data is not None:
+            ptr, keep = self._data_plane(data, grid, "build_dense")
+            rc = N.lib().vhx_build_tree_dense_data(self._h, ctypes.byref(d), ptr, on_device)
+            del keep
+        else:
+            build = N.lib().vhx_build_tree_dense_simplified if simplify else N.lib().vhx_build_tree_dense
+            rc = build(self._h, ctypes.byref(d), on_device)
         if rc in _TREE_ERRORS:
             raise _TREE_ERRORS[rc](f"size {size} brick_dim {brick_dim}")
         self._check(rc)
         self._tree = _BuiltOnDevice()
+        if data is not None and simplify:
+            self.simplify()
 
     def tree_counts(self):
         """vhx_tree_counts: sizes and counts of the uploaded tree."""
@@ -332,11 +361,15 @@ class Raytracer:
         self._check(N.lib().vhx_get_voxels(self._h, p.ctypes.data, p.shape[0], out.ctypes.data, 0))
         return out
 
-    def read_dense(self, origin=(0, 0, 0), extents=None, out=None):
+    def read_dense(self, origin=(0, 0, 0), extents=None, out=None, data=False):
         """vhx_read_dense: the box at `origin` (x, y, z) with `extents` (gx, gy, gz; None = the whole root cube) as a
         dense grid of shape (gz, gy, gx) of packed albedos, 0 where there is no visible voxel -- the inverse of
         build_dense. `out` (optional) receives it: a C-contiguous uint32 numpy array, or a contiguous int32 / uint32
-        torch tensor on this context's device (synchronised like get's); without it a numpy array is returned."""
+        torch tensor on this context's device (synchronised like get's); without it a numpy array is returned.
+        data=True (vhx_read_dense_data) returns (albedo, data): the second grid holds every voxel's user data value,
+        0 where it has none, read in the same walk of the tree. An array or tensor passed as `data` (of out's kind and
+        shape; with out=None a numpy array) receives the data plane and is returned beside the albedo."""
+        want_data = data is not False and data is not None
         ox, oy, oz = (int(v) for v in origin)
         if extents is None:
             extents = (self.tree_counts().boxtree_size,) * 3
@@ -344,29 +377,59 @@ class Raytracer:
         if min(ox, oy, oz) < 0 or min(gx, gy, gz) < 0:
             raise ValueError("read_dense: origin and extents are unsigned")
         if out is None:
-            out = np.empty((gz, gy, gx), np.uint32)
+            if want_data and hasattr(data, "data_ptr"):
+                import torch
+                out = torch.empty((gz, gy, gx), dtype=data.dtype, device=data.device)
+            else:
+                out = np.empty((gz, gy, gx), np.uint32)
+        if want_data:
+            if data is True:
+                if hasattr(out, "data_ptr"):
+                    import torch
+                    data = torch.empty_like(out)
+                else:
+                    data = np.empty((gz, gy, gx), np.uint32)
+            if tuple(data.shape) != (gz, gy, gx):
+                raise ValueError(f"read_dense: data has shape {tuple(data.shape)}, the box needs {(gz, gy, gx)}")
+            if hasattr(data, "data_ptr") != hasattr(out, "data_ptr"):
+                raise TypeError("read_dense: out and data are both arrays or both tensors")
         if tuple(out.shape) != (gz, gy, gx):
             raise ValueError(f"read_dense: out has shape {tuple(out.shape)}, the box needs {(gz, gy, gx)}")
         box = N.DenseOut(ox, oy, oz, gx, gy, gz, None)
         if hasattr(out, "data_ptr"):
             box.albedo = self._device_tensor(out, "read_dense").data_ptr()
+            if want_data:
+                dptr = self._device_tensor(data, "read_dense").data_ptr()
+                self._check(N.lib().vhx_read_dense_data(self._h, ctypes.byref(box), dptr, 1))
+                self.sync()
+                return out, data
             self._check(N.lib().vhx_read_dense(self._h, ctypes.byref(box), 1))
             self.sync()
             return out
         if out.dtype != np.uint32 or not out.flags.c_contiguous:
             raise TypeError("read_dense: out is a C-contiguous uint32 array")
         box.albedo = out.ctypes.data
+        if want_data:
+            if data.dtype != np.uint32 or not data.flags.c_contiguous:
+                raise TypeError("read_dense: data is a C-contiguous uint32 array")
+            self._check(N.lib().vhx_read_dense_data(self._h, ctypes.byref(box), data.ctypes.data, 0))
+            return out, data
         self._check(N.lib().vhx_read_dense(self._h, ctypes.byref(box), 0))
         return out
 
-    def write_dense(self, grid, origin=(0, 0, 0), mode="replace"):
+    def write_dense(self, grid, origin=(0, 0, 0), mode="replace", data=None):
         """vhx_write_dense: the box at `origin` (x, y, z) with the extents of `grid` (shape (gz, gy, gx), packed albedos as
         for build_dense) replaced on the device, in place -- the inverse of read_dense. mode "replace": every voxel of
         the box becomes the grid's, alpha 0 clears; "insert": grid voxels with alpha 0 leave the tree as it is. `grid` is
         a uint32 numpy array (copied to the device first) or a contiguous int32 / uint32 torch tensor on this context's
         device, read in place (torch's current stream is synchronised before the call). Owner context only; the call
         returns when the tree is ready. Slots are never reused: orphans() counts the unlinked ones and compact() drops
-        them."""
+        them.
+        `data` (vhx_write_dense_data) gives the box's voxels user data values, 0 = none: a plane of the same kind,
+        shape and device as `grid`, or an integer that every voxel of the box gets. A voxel of the box is then an entry
+        where it has a colour or a data value ("replace" clears where it has neither, "insert" leaves the tree alone
+        there), and a written voxel is replaced wholesale: an old data value does not survive under a colour written
+        without one. New data values follow the data palette in the box's insert order."""
         modes = {"replace": N.VHX_WRITE_REPLACE, "insert": N.VHX_WRITE_INSERT}
         box = N.DenseIn()
         box.ox, box.oy, box.oz = (int(v) for v in origin)
@@ -382,16 +445,41 @@ class Raytracer:
                 raise TypeError("write_dense: an array of shape (gz, gy, gx)")
             box.albedo, on_device = grid.ctypes.data, 0
         box.gz, box.gy, box.gx = (int(v) for v in grid.shape)
-        self._check(N.lib().vhx_write_dense(self._h, ctypes.byref(box), on_device))
+        if data is None:
+            self._check(N.lib().vhx_write_dense(self._h, ctypes.byref(box), on_device))
+        elif isinstance(data, (int, np.integer)):
+            self._check(N.lib().vhx_write_dense_data(self._h, ctypes.byref(box), None, int(data), on_device))
+        else:
+            ptr, keep = self._data_plane(data, grid, "write_dense")
+            self._check(N.lib().vhx_write_dense_data(self._h, ctypes.byref(box), ptr, 0, on_device))
+            del keep
 
-    def fill_box(self, origin, extents, albedo):
+    def fill_box(self, origin, extents, albedo, data=0):
         """vhx_write_dense without a grid: every voxel of the box at `origin` with `extents` (gx, gy, gz) becomes the
-        packed colour `albedo`; 0 (or any colour with alpha 0) clears the box."""
+        packed colour `albedo`; 0 (or any colour with alpha 0) clears the box. `data` (vhx_write_dense_data) is the
+        user data value every voxel of the box gets beside the colour, 0 = none -- fill_box(o, e, 0, 7) writes
+        data-only voxels, fill_box(o, e, 0, 0) clears -- or a plane of shape (gz, gy, gx) with a value per voxel (a
+        uint32 numpy array or a device tensor)."""
         box = N.DenseIn()
         box.ox, box.oy, box.oz = (int(v) for v in origin)
         box.gx, box.gy, box.gz = (int(v) for v in extents)
         box.mode, box.fill, box.albedo = N.VHX_WRITE_REPLACE, int(albedo), None
-        self._check(N.lib().vhx_write_dense(self._h, ctypes.byref(box), 0))
+        if isinstance(data, (int, np.integer)):
+            if int(data) == 0:
+                self._check(N.lib().vhx_write_dense(self._h, ctypes.byref(box), 0))
+            else:
+                self._check(N.lib().vhx_write_dense_data(self._h, ctypes.byref(box), None, int(data), 0))
+            return
+        if tuple(data.shape) != (box.gz, box.gy, box.gx):
+            raise ValueError(f"fill_box: data has shape {tuple(data.shape)}, the box needs {(box.gz, box.gy, box.gx)}")
+        if hasattr(data, "data_ptr"):
+            ptr, keep, on_device = self._device_tensor(data, "fill_box").data_ptr(), data, 1
+        else:
+            from .boxtree import _dense_data
+            keep = _dense_data(data, data.shape)
+            ptr, on_device = keep.ctypes.data, 0
+        self._check(N.lib().vhx_write_dense_data(self._h, ctypes.byref(box), ptr, 0, on_device))
+        del keep
 
     def orphans(self):
         """vhx_tree_orphans: (nodes, bricks) that write_dense / fill_box unlinked since the last upload or build; their
