@@ -351,7 +351,45 @@ int vhx_write_dense(vhx_ctx *ctx, const vhx_dense_in *box, int on_device);
  * for bit. Past 65,535 data values: VHX_E_CAPACITY, tree unchanged. Everything else -- Leaf nodes, Parted bricks,
  * unlinked slots, ordering, owner only, refusals -- is vhx_write_dense's contract. */
 int vhx_write_dense_data(vhx_ctx *ctx, const vhx_dense_in *box, const uint32_t *data, uint32_t fill_data, int on_device);
-/* Node and brick slots that vhx_write_dense has unlinked since the last upload or build. */
+/* A list of points written into the tree, or cleared from it, on the device and in place: the batched form of
+ * BoxTree::insert(position, value) / clear(position), and the counterpart of vhx_get_voxels. The work and the scratch
+ * follow the points and the bricks they touch, not their bounding box. */
+typedef struct vhx_points_in {
+    uint64_t n;                 /* points; 0 succeeds and does nothing; at most 2^31 */
+    const uint32_t *positions;  /* 3 u32 per point: x, y, z (as vhx_get_voxels) */
+    const uint32_t *albedo;     /* n packed colours, or NULL: every point's albedo word is `fill` */
+    const uint32_t *data;       /* n data values (0 = none), or NULL: every point's data word is `fill_data` */
+    uint32_t fill, fill_data;
+    uint32_t mode;              /* VHX_WRITE_REPLACE / VHX_WRITE_INSERT */
+    uint32_t reserved0;
+} vhx_points_in;
+/* All non-null arrays live in the same place, host (copied first) or device (on_device = 1: read in place, never
+ * written). A point's entry follows the rule of vhx_build_tree_dense_data from its albedo word a and data word d: none,
+ * Visual, Informative or Complex; an albedo with alpha byte 0 never reaches the colour palette. VHX_WRITE_REPLACE: every
+ * point is effective, and a point whose entry is none clears its voxel (albedo == NULL, data == NULL, fill == 0,
+ * fill_data == 0 is a batched clear). VHX_WRITE_INSERT: a point whose entry is none is not effective and touches
+ * nothing. The result is that of the loop `for i in 0..n: insert / clear(positions[i])`: where several effective points
+ * name one voxel, the one with the highest index decides it, whether it writes or clears. Afterwards vhx_read_dense and
+ * vhx_read_dense_data of the root cube are what they were with the decided voxels replaced, vhx_get_voxels of a written
+ * voxel is ci | di << 16 (0xFFFF for a half that is none; the lowest indices that hold the values), a cleared voxel
+ * reads VHX_EMPTY, every other voxel reads as before; a written voxel is replaced wholesale. New colours follow
+ * color_count in the order of their first appearance in the list (lowest point index), counted over all effective
+ * points, overridden ones included; new data values likewise after data_count; an entry of data_palette equal to 0 is
+ * never matched; solid_values never changes. Structure as vhx_write_dense, with "a cube that holds an effective point"
+ * for "a cube the box meets": touched leaves become Leaf nodes, touched bricks Parted bricks (rewritten in their slot,
+ * or given a new one whose undecided cells hold the old raw value), emptied bricks and nodes are unlinked up to the
+ * root, missing path nodes are created. The touched cubes of a level are ordered by their parent's order, then by
+ * sectant; new nodes follow node_count level by level from the top in that order, new bricks follow brick_count in
+ * (touched leaf cube, sectant) order: the image is a pure function of the old image and the list. Slots are not
+ * reused (vhx_tree_orphans). Ordering and refusals are vhx_write_dense's: owner context only, frames submitted before
+ * the call see the old tree, frames after it the new one, the call returns when the tree is ready, and a refused call
+ * leaves every buffer as it was -- VHX_E_STATE before any upload, on a shared context, while node MIPs are set, or where
+ * the tree under an effective point is not of canonical depth; VHX_E_INVALID_ARG for a null pts, null positions with
+ * n > 0, more than 2^31 points, an unknown mode, or any position outside the root cube (found on the device; ineffective
+ * points count too); VHX_E_CAPACITY past 65,535 colours or data values, 2^31 bricks, 2^32 nodes or 2^28 touched leaf
+ * cubes. */
+int vhx_set_voxels(vhx_ctx *ctx, const vhx_points_in *pts, int on_device);
+/* Node and brick slots that vhx_write_dense and vhx_set_voxels have unlinked since the last upload or build. */
 int vhx_tree_orphans(const vhx_ctx *ctx, uint32_t *nodes, uint32_t *bricks);
 /* Rewrites the resident tree on the device without its unreachable slots and in the builders' numbering: the image of
  * vhx_flat_compact (vhx_boxtree.h) of the tree, bit for bit. Nodes are renumbered breadth-first from the root, Parted

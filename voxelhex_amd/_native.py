@@ -73,6 +73,11 @@ class DenseIn(ctypes.Structure):  # vhx_dense_in
                 ("mode", c_u32), ("fill", c_u32), ("albedo", c_void_p)]
 
 
+class PointsIn(ctypes.Structure):  # vhx_points_in
+    _fields_ = [("n", c_u64), ("positions", c_void_p), ("albedo", c_void_p), ("data", c_void_p), ("fill", c_u32),
+                ("fill_data", c_u32), ("mode", c_u32), ("reserved0", c_u32)]
+
+
 class Range(ctypes.Structure):
     _fields_ = [("buffer_id", ctypes.c_int32), ("reserved0", c_u32), ("elem_offset", c_u64), ("elem_count", c_u64),
                 ("src", c_void_p)]
@@ -133,6 +138,7 @@ SIGNATURES = [
     ("vhx_build_tree_dense_data", c_int, [c_void_p, P(DenseDesc), c_void_p, c_int]),
     ("vhx_read_dense_data", c_int, [c_void_p, P(DenseOut), c_void_p, c_int]),
     ("vhx_write_dense_data", c_int, [c_void_p, P(DenseIn), c_void_p, c_u32, c_int]),
+    ("vhx_set_voxels", c_int, [c_void_p, P(PointsIn), c_int]),
     ("vhx_tree_orphans", c_int, [c_void_p, P(c_u32), P(c_u32)]),
     ("vhx_compact_tree", c_int, [c_void_p, P(c_u32), P(c_u32)]),
     ("vhx_simplify_tree", c_int, [c_void_p, P(c_u32), P(c_u32)]),

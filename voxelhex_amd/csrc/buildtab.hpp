@@ -106,10 +106,13 @@ __device__ inline uint32_t color_lookup(const ColorTable t, uint32_t c) {
 
 
 // ---- scans over the occupancy words of a level: MODE 0 "the node exists" (the root always does), MODE 1 its bricks
-// (MODE 2: of a simplified build, from SimpTable::linfo)
+// (MODE 2: of a simplified build, from SimpTable::linfo; MODE 3: the word is a count below 2^32, vhx_points.hip)
 template <int MODE>
 __device__ inline uint32_t scan_value(u64 w, bool root) {
-    return MODE == 0 ? (uint32_t)(w != 0 || root) : MODE == 1 ? (uint32_t)__popcll(w) : (uint32_t)(w & 0x7Fu);
+    return MODE == 0   ? (uint32_t)(w != 0 || root)
+           : MODE == 1 ? (uint32_t)__popcll(w)
+           : MODE == 2 ? (uint32_t)(w & 0x7Fu)
+                       : (uint32_t)w;
 }
 
 // inclusive scan over the block's 256 threads (lds: 4 words)

@@ -1,6 +1,6 @@
 // Internal context of libvhx, shared by the translation units of the device side: vhx_device.hip (tracing), vhx_tree.hip
 // (the device tree), vhx_ctx.hip (contexts, ordering, settings), vhx_mgpu.hip, vhx_build.hip, vhx_query.hip,
-// vhx_edit.hip, vhx_compact.hip, vhx_simplify.hip and vhx_palette.hip.
+// vhx_edit.hip, vhx_points.hip, vhx_compact.hip, vhx_simplify.hip and vhx_palette.hip.
 // Not part of the ABI: callers see vhx_ctx only as an opaque pointer (include/vhx.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -145,6 +145,15 @@ struct vhx_ctx {
     struct EditScratch {
         DevBuf oldn, aft, need, rank, nmask, first, ctl;
     } edit;
+    // vhx_set_voxels (vhx_points.hip): the device copy of host arrays; per point its touched cube in the current level
+    // and, grouped by touched brick, the point indices; per level of the sparse lists of touched cubes the sectant mask,
+    // the first touched child, the old node, the occupancy after the write and the "needs a new node" words with their
+    // ranks; per touched leaf its old type and uniform brick, new-brick mask and first new brick; per touched brick its
+    // place, point count, segment and flags; the counters read back. Reset by each call; the tables and the scans' block
+    // sums are the build's
+    struct PointsScratch {
+        DevBuf in, cur, idx, mask, first, oldn, aft, need, rank, ltype, lu, nmask, bfirst, binfo, bcnt, bseg, bflag, ctl;
+    } points;
     // vhx_compact_tree (vhx_compact.hip): new index of every old node and the inverse, per new node the mask of its
     // child entries with the rank of its first child and the mask of its Parted entries with its first new brick, the
     // new index of every old brick (the claims) and the inverse, and the counters read back. Reset by each call; the

@@ -232,7 +232,11 @@ void vhx_destroy(vhx_ctx *c) {
                       &c->shadow_args, &c->tail_list[0], &c->tail_list[1], &c->tail_mask, &c->build.occ, &c->build.rank,
                       &c->build.first, &c->build.part, &c->build.table, &c->build.ctl, &c->build.grid,
                       &c->build.simp, &c->build.dtable, &c->work, &c->query, &c->edit.oldn, &c->edit.aft, &c->edit.need,
-                      &c->edit.rank, &c->edit.nmask, &c->edit.first, &c->edit.ctl, &c->compact.new_of,
+                      &c->edit.rank, &c->edit.nmask, &c->edit.first, &c->edit.ctl, &c->points.in, &c->points.cur,
+                      &c->points.idx, &c->points.mask, &c->points.first, &c->points.oldn, &c->points.aft,
+                      &c->points.need, &c->points.rank, &c->points.ltype, &c->points.lu, &c->points.nmask,
+                      &c->points.bfirst, &c->points.binfo, &c->points.bcnt, &c->points.bseg, &c->points.bflag,
+                      &c->points.ctl, &c->compact.new_of,
                       &c->compact.old_of, &c->compact.nmask, &c->compact.nrank, &c->compact.bmask,
                       &c->compact.bfirst, &c->compact.bnew, &c->compact.bsrc, &c->compact.ctl, &c->simplify.binfo,
                       &c->simplify.pmask, &c->simplify.gmask, &c->simplify.bfirst, &c->simplify.ent,

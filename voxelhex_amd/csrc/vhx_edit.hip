@@ -28,27 +28,18 @@
 // The emission writes the derived state of what it writes (headers, bitmaps of written bricks, child records of written
 // entries) itself: a bitmap is the ballot the leaf pass already needs to decide whether the brick exists. Every global
 // write is a plain store; the atomics are ORs, minima, table claims and counts, as in vhx_build.hip, so the image does
-// not depend on scheduling.
+// not depend on scheduling. What vhx_points.hip uses as well (the counters, the view of the tree's buffers, k_edit_seed,
+// k_edit_pal_compact, k_edit_pal_shift) is in edittab.hpp.
 #include <algorithm>
 #include <string>
 
 #include "../../include/vhx.h"
 #include "buildtab.hpp"
 #include "ctx.hpp"
+#include "edittab.hpp"
 #include "treewalk.hpp"
 
 namespace {
-
-constexpr uint32_t NONE = 0xFFFFFFFFu;
-constexpr u64 NEW_BASE = 1ull << 32;  // first indices of the box's colours: above every palette index
-
-struct EditCtl {
-    BuildCtl b;  // level_total: new nodes per level; brick_total: new bricks; ncolors starts at the palette's count
-    uint32_t bad;  // the tree under the box is not of canonical depth
-    uint32_t orphan_nodes, orphan_bricks;
-    uint32_t pad;
-    BuildCtl d;  // vhx_write_dense_data: the data table's ncolors (starts at data_count), overflow and ncompact
-};
 
 struct Lattice {
     uint32_t lo[3], n[3];  // first cube and cubes per axis
@@ -64,17 +55,6 @@ struct EditP {
     uint64_t total;  // cells of all levels
     Lattice lv[MAX_LEVELS];
     uint32_t new_base[MAX_LEVELS];  // emission: index of the level's first new node
-};
-
-struct TreeP {
-    uint32_t *type;
-    u64 *ocbits;
-    uint32_t *children, *voxels;
-    const uint32_t *solid, *color, *data;
-    uint4 *hdr;
-    u64 *occ;
-    uint4 *rec;  // null above brick_dim 4
-    uint32_t node_count, brick_count, solid_count, color_count, data_count, occ_words;  // before the write
 };
 
 struct Scratch {
@@ -132,29 +112,6 @@ __global__ __launch_bounds__(256) void k_edit_walk(EditP p, TreeP t, Scratch s, 
     }
     s.oldn[gid] = node;
     if (bad) atomicOr(&ctl->bad, 1u);
-}
-
-// DATA = 1 seeds the data table from data_palette: an entry equal to 0 is skipped (0 is the free key, and a written data
-// value is never 0)
-template <int DATA>
-__global__ __launch_bounds__(256) void k_edit_seed(ColorTable t, const uint32_t *pal, uint32_t n, EditCtl *ctl) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i == 0) (DATA ? ctl->d : ctl->b).ncolors = n;  // the leaf pass counts the claims of new values on top
-    if (i >= n) return;
-    const uint32_t c = pal[i];
-    if (DATA ? c == 0 : (c >> 24) == 0) return;  // never looked up: a written voxel's colour has a non-zero alpha byte
-    uint32_t h = color_hash(c);
-    for (uint32_t probe = 0; probe < TAB_SLOTS; ++probe, h = (h + 1) & TAB_MASK) {
-        uint32_t k = t.keys[h];
-        if (k == 0) {
-            k = atomicCAS(&t.keys[h], 0u, c);
-            if (k == 0) k = c;
-        }
-        if (k == c) {
-            atomicMin(&t.vals[h], (u64)i);  // a colour the palette holds twice: its lowest index
-            return;
-        }
-    }
 }
 
 // The touched leaves. EMIT = 0 analyses (reads the tree only), EMIT = 1 writes; both derive a brick's bitmap after the
@@ -353,26 +310,6 @@ __global__ __launch_bounds__(256) void k_edit_reduce(EditP p, TreeP t, Scratch s
     if (m == 0 && node != NONE && lv != 0) atomicAdd(&ctl->orphan_nodes, 1u);
 }
 
-// the new colours of the table (first index at or above NEW_BASE), compacted for k_pal_rank; `b` is the table's counters
-__global__ __launch_bounds__(256) void k_edit_pal_compact(ColorTable t, BuildCtl *b) {
-    const uint32_t h = blockIdx.x * 256 + threadIdx.x;
-    if (h >= TAB_SLOTS) return;
-    const uint32_t k = t.keys[h];
-    if (k == 0 || t.vals[h] < NEW_BASE) return;
-    const uint32_t pos = atomicAdd(&b->ncompact, 1u);  // any order: the ranks come from the first indices
-    if (pos >= PAL_CAP) return;
-    t.ckey[pos] = k;
-    t.cidx[pos] = t.vals[h];
-    t.cslot[pos] = h;
-}
-
-// k_pal_rank left each new colour's rank among the new ones in its slot: its palette index is color_count further
-__global__ __launch_bounds__(256) void k_edit_pal_shift(ColorTable t, const BuildCtl *b, uint32_t color_count) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= min(b->ncompact, PAL_CAP)) return;
-    t.vals[t.cslot[i]] += color_count;
-}
-
 // level lv, one thread per (cube, sectant): the node's type, occupancy and header, and for lv < D its entries inside
 // the lattice (a new node's other entries are empty, an old node's stay). A node that lost everything becomes Nothing.
 __global__ __launch_bounds__(256) void k_edit_nodes(EditP p, TreeP t, Scratch s, uint32_t lv) {
@@ -408,28 +345,6 @@ __global__ __launch_bounds__(256) void k_edit_nodes(EditP p, TreeP t, Scratch s,
     }
     t.children[at] = e;
     if (t.rec) t.rec[at] = make_uint4(e, 0u, 0u, 0u);
-}
-
-TreeP tree_of(const vhx_ctx *c, const vhx_tree_desc &d) {
-    const TreeStore &s = *c->tree;
-    TreeP t{};
-    t.type = (uint32_t *)s.raw[VHX_BUF_NODE_TYPE].ptr;
-    t.ocbits = (u64 *)s.raw[VHX_BUF_NODE_OCBITS].ptr;
-    t.children = (uint32_t *)s.raw[VHX_BUF_NODE_CHILDREN].ptr;
-    t.voxels = (uint32_t *)s.raw[VHX_BUF_VOXELS].ptr;
-    t.solid = (const uint32_t *)s.raw[VHX_BUF_SOLID_VALUES].ptr;
-    t.color = (const uint32_t *)s.raw[VHX_BUF_COLOR_PALETTE].ptr;
-    t.data = (const uint32_t *)s.raw[VHX_BUF_DATA_PALETTE].ptr;
-    t.hdr = (uint4 *)s.hdr.ptr;
-    t.occ = (u64 *)s.brick_occ.ptr;
-    t.rec = d.brick_dim * d.brick_dim * d.brick_dim <= 64 ? (uint4 *)s.child_rec.ptr : nullptr;
-    t.node_count = d.node_count;
-    t.brick_count = d.brick_count;
-    t.solid_count = d.solid_count;
-    t.color_count = d.color_count;
-    t.data_count = d.data_count;
-    t.occ_words = s.occ_words;
-    return t;
 }
 
 // both dense writes: `with_data` is vhx_write_dense_data with a data plane or a data fill

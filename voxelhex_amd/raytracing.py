@@ -481,6 +481,61 @@ class Raytracer:
         self._check(N.lib().vhx_write_dense_data(self._h, ctypes.byref(box), ptr, 0, on_device))
         del keep
 
+    def set_voxels(self, positions, albedo=None, data=None, mode="replace"):
+        """vhx_set_voxels: a list of voxels written into the device tree in place -- the batched BoxTree.insert / clear,
+        and the counterpart of get. `positions` is an (n, 3) integer numpy array (x, y, z per row; copied to the device
+        first), or a contiguous int32 / uint32 torch tensor of that shape on this context's device, read in place
+        (torch's current stream is synchronised before the call, as for get and write_dense). `albedo` and `data` are
+        arrays of the same kind with n packed colours / user data values (0 = none), or integers that every point gets
+        (None = 0). A point with a colour or a data value is written, replacing its voxel wholesale; one with neither
+        clears its voxel under mode "replace" and touches nothing under "insert". The result is that of the loop over
+        the list: where points repeat a position the last one decides. New colours and data values follow the palettes
+        in list order. Owner context only; the call returns when the tree is ready; slots are never reused (orphans(),
+        compact()). Cost and scratch follow the points and the bricks they touch, not their bounding box."""
+        modes = {"replace": N.VHX_WRITE_REPLACE, "insert": N.VHX_WRITE_INSERT}
+        pts = N.PointsIn()
+        pts.mode = modes[mode] if mode in modes else int(mode)
+        keep = []
+        if hasattr(positions, "data_ptr"):
+            if positions.dim() != 2 or positions.shape[1] != 3:
+                raise TypeError("set_voxels: positions of shape (n, 3)")
+            p = self._device_tensor(positions, "set_voxels")
+            n, on_device = int(p.shape[0]), 1
+            pts.positions = p.data_ptr()
+        else:
+            p = np.asarray(positions)
+            if p.ndim != 2 or p.shape[1] != 3 or p.dtype.kind not in "iu":
+                raise TypeError("set_voxels: an integer array of shape (n, 3)")
+            if p.size and (int(p.min()) < 0 or int(p.max()) > 0xFFFFFFFF):
+                raise ValueError("set_voxels: positions are unsigned 32-bit")
+            p = np.ascontiguousarray(p.astype(np.uint32, copy=False))
+            n, on_device = int(p.shape[0]), 0
+            pts.positions = p.ctypes.data
+        keep.append(p)
+        pts.n = n
+        for name, words in (("albedo", albedo), ("data", data)):
+            fill = "fill" if name == "albedo" else "fill_data"
+            if words is None or isinstance(words, (int, np.integer)):
+                setattr(pts, fill, int(words or 0))
+                continue
+            if hasattr(words, "data_ptr") != bool(on_device):
+                raise TypeError(f"set_voxels: positions and {name} are both arrays or both device tensors")
+            if tuple(words.shape) != (n,):
+                raise ValueError(f"set_voxels: {name} has shape {tuple(words.shape)}, the list needs {(n,)}")
+            if on_device:
+                w = self._device_tensor(words, "set_voxels")
+                setattr(pts, name, w.data_ptr())
+            else:
+                w = np.ascontiguousarray(words, np.uint32)
+                setattr(pts, name, w.ctypes.data)
+            keep.append(w)
+        self._check(N.lib().vhx_set_voxels(self._h, ctypes.byref(pts), on_device))
+        del keep
+
+    def clear_voxels(self, positions):
+        """vhx_set_voxels without values: every listed voxel is cleared (the batched BoxTree.clear)."""
+        self.set_voxels(positions, 0, 0, "replace")
+
     def orphans(self):
         """vhx_tree_orphans: (nodes, bricks) that write_dense / fill_box unlinked since the last upload or build; their
         slots are not reused (compact() drops them)."""
