@@ -19,6 +19,8 @@
  *                           examples/gpu_render.rs:196-257 / benches/performance.rs:29-66
  *   vhx_trace_rays       <- BoxTree::get_by_ray (src/raytracing/cpu.rs:296) over an explicit batch of rays
  *   vhx_get_voxels       <- BoxTree::get (src/boxtree/mod.rs:223-317) over a batch of positions
+ *   vhx_list_voxels      <- no single counterpart (the reference would iterate BoxTree::get over the box): the
+ *                           occupied voxels of a box as a list, the inverse of vhx_set_voxels
  *   vhx_last_error       <- the Result<_, ()> / expect() error paths of the plugin (src/raytracing/bevy/streaming/mod.rs:63-73)
  *
  * Conventions: every function returns 0 on success or a negative VHX_E_* code; a message is kept per context
@@ -389,6 +391,41 @@ typedef struct vhx_points_in {
  * points count too); VHX_E_CAPACITY past 65,535 colours or data values, 2^31 bricks, 2^32 nodes or 2^28 touched leaf
  * cubes. */
 int vhx_set_voxels(vhx_ctx *ctx, const vhx_points_in *pts, int on_device);
+/* The occupied voxels of a box of the tree as a list: the sparse form of vhx_read_dense_data and the inverse of
+ * vhx_set_voxels. The work and the scratch follow the nodes and bricks under the box, not its volume. */
+typedef struct vhx_points_out {
+    uint32_t ox, oy, oz;     /* min corner of the box in the tree */
+    uint32_t gx, gy, gz;     /* extents >= 1; the box must lie inside the root cube */
+    uint64_t capacity;       /* entries each non-null array can hold; 0 = count only */
+    uint32_t *positions;     /* 3 u32 per entry (x, y, z), or NULL */
+    uint32_t *albedo;        /* 1 u32 per entry, or NULL */
+    uint32_t *data;          /* 1 u32 per entry, or NULL */
+    uint64_t *count;         /* HOST memory, never NULL: the number of listed voxels in the box */
+} vhx_points_out;
+/* With (a, d) the two words vhx_read_dense_data writes for a voxel of the box, the voxel is listed exactly when
+ * (a, d) != (0, 0), and its entry is (position, a, d); every corner that call decides is decided here the same way.
+ * The list is ascending in key(x, y, z), a fixed permutation of the bits of the position: with boxtree_size =
+ * brick_dim * 4^k, the k sectant digits of the position from the root down, the root's most significant -- the digit
+ * of a node 2^lg voxels wide is ((x >> (lg-2)) & 3) | ((y >> (lg-2)) & 3) << 2 | ((z >> (lg-2)) & 3) << 4, and the last
+ * digit is the brick's sectant inside the smallest leaf -- and below them the 3 * log2(brick_dim) bits of the flat
+ * cell index (x & m) + (y & m) * brick_dim + (z & m) * brick_dim^2, m = brick_dim - 1. That is the order in which a
+ * depth-first walk of the unsimplified canonical tree meets the voxels; it depends on the position alone, so a Parted
+ * build, its simplified form and an edited tree with orphaned slots give the same list for the same voxels, bit for bit.
+ * *count always receives the total for the box; the first min(*count, capacity) entries of the list are written and
+ * nothing past them. capacity == 0 writes no array (the three pointers may then be anything); with capacity > 0 any of
+ * the three arrays may be NULL to skip that field. on_device = 0: the arrays are host memory. 1: device memory, written
+ * in place; the non-null arrays must not overlap each other (VHX_E_INVALID_ARG before anything is written). `count` is
+ * host memory in both cases, and the call returns when count and arrays are complete. Ordered like vhx_read_dense (a
+ * trace-like read): allowed on shared contexts, it sees every write submitted before it and none after; nothing of the
+ * tree is written. A refused call leaves arrays and *count untouched: VHX_E_STATE before any upload; VHX_E_INVALID_ARG
+ * for a null q or count, an extent of 0, a box outside the root cube, overlapping device arrays; VHX_E_CAPACITY for a
+ * box of 2^48 voxels or more (ranks are 64-bit) and for a brick_dim above 1024; VHX_E_STATE where a Leaf or
+ * UniformLeaf reached under the box lies above the smallest leaf level (a brick stretched over a larger cube;
+ * vhx_write_dense refuses the same trees). A LOD-cut or streamed view whose absent children are VHX_EMPTY entries is
+ * accepted: those regions read as empty. With host arrays the listed entries are staged in device memory that the
+ * context keeps (as vhx_read_dense keeps its grid). vhx_flat_list_voxels (vhx_boxtree.h) is the same call over a
+ * host image. */
+int vhx_list_voxels(vhx_ctx *ctx, const vhx_points_out *q, int on_device);
 /* Node and brick slots that vhx_write_dense and vhx_set_voxels have unlinked since the last upload or build. */
 int vhx_tree_orphans(const vhx_ctx *ctx, uint32_t *nodes, uint32_t *bricks);
 /* Rewrites the resident tree on the device without its unreachable slots and in the builders' numbering: the image of

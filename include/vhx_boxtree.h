@@ -30,6 +30,7 @@
  *   vhx_flat_simplify          <- that image after BoxTree::simplify(ROOT, recursive), as insert / clear leave a tree
  *                                 with auto-simplify on
  *   vhx_flat_compact_palette   <- no reference counterpart: an edited image with the colour palette of a fresh build
+ *   vhx_flat_list_voxels       <- no single counterpart (BoxTree::get iterated over a box): its occupied voxels as a list
  *
  * Tree type parameter: T = u32 (the reference default, BoxTree<T = u32>, src/boxtree/types.rs:219).
  */
@@ -239,6 +240,13 @@ int vhx_flat_simplify(const vhx_tree_desc *tree, vhx_flat **out);
  * UniformLeaf so deep that a cell of its bricks would be smaller than a voxel (its cubes would have no corner of their
  * own). Duplicate palette entries are accepted. Node MIPs are not carried over. */
 int vhx_flat_compact_palette(const vhx_tree_desc *tree, vhx_flat **out);
+/* vhx_list_voxels (vhx.h, which states the contract) over the host image `tree`, with host arrays: the CPU counterpart
+ * of the device call, bit for bit in *count and in every array. It is the plain walk -- depth-first from node 0, sectants
+ * ascending, the cells of a brick in flat order, clipped to the box -- with a voxel's two words computed as
+ * vhx_read_dense_data computes them (a Leaf's cell that points to empty, by the image's palettes, reads as empty).
+ * Refusals as the device call, with VHX_E_INVALID_ARG also for a null tree, null node arrays, a count of 0 nodes and a
+ * size that is not brick_dim * 4^k. */
+int vhx_flat_list_voxels(const vhx_tree_desc *tree, const vhx_points_out *q);
 void vhx_flat_free(vhx_flat *flat);
 
 /* MagicaVoxel .vox import — BoxTree::<u32>::load_vox_file(filename, brick_dimension) (src/convert/magicavoxel.rs:

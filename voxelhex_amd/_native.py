@@ -78,6 +78,12 @@ class PointsIn(ctypes.Structure):  # vhx_points_in
                 ("fill_data", c_u32), ("mode", c_u32), ("reserved0", c_u32)]
 
 
+class PointsOut(ctypes.Structure):  # vhx_points_out
+    _fields_ = [("ox", c_u32), ("oy", c_u32), ("oz", c_u32), ("gx", c_u32), ("gy", c_u32), ("gz", c_u32),
+                ("capacity", c_u64), ("positions", c_void_p), ("albedo", c_void_p), ("data", c_void_p),
+                ("count", P(c_u64))]
+
+
 class Range(ctypes.Structure):
     _fields_ = [("buffer_id", ctypes.c_int32), ("reserved0", c_u32), ("elem_offset", c_u64), ("elem_count", c_u64),
                 ("src", c_void_p)]
@@ -139,6 +145,7 @@ SIGNATURES = [
     ("vhx_read_dense_data", c_int, [c_void_p, P(DenseOut), c_void_p, c_int]),
     ("vhx_write_dense_data", c_int, [c_void_p, P(DenseIn), c_void_p, c_u32, c_int]),
     ("vhx_set_voxels", c_int, [c_void_p, P(PointsIn), c_int]),
+    ("vhx_list_voxels", c_int, [c_void_p, P(PointsOut), c_int]),
     ("vhx_tree_orphans", c_int, [c_void_p, P(c_u32), P(c_u32)]),
     ("vhx_compact_tree", c_int, [c_void_p, P(c_u32), P(c_u32)]),
     ("vhx_simplify_tree", c_int, [c_void_p, P(c_u32), P(c_u32)]),
@@ -221,6 +228,7 @@ SIGNATURES = [
     ("vhx_flat_compact", c_int, [P(TreeDesc), P(c_void_p)]),
     ("vhx_flat_simplify", c_int, [P(TreeDesc), P(c_void_p)]),
     ("vhx_flat_compact_palette", c_int, [P(TreeDesc), P(c_void_p)]),
+    ("vhx_flat_list_voxels", c_int, [P(TreeDesc), P(PointsOut)]),
     ("vhx_boxtree_switch_mips", c_int, [c_void_p, c_int]),
     ("vhx_boxtree_set_mip_method", c_int, [c_void_p, c_u32, c_u32, c_f32]),
     ("vhx_boxtree_set_mip_color_threshold", c_int, [c_void_p, c_u32, c_f32]),

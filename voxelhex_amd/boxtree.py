@@ -310,9 +310,55 @@ def _palette_compacted(image):
     return FlatTree(h.value)
 
 
+def _list_box(size, origin, extents):
+    """(ox, oy, oz, gx, gy, gz) of a list / count call; extents None = the whole root cube."""
+    ox, oy, oz = (int(v) for v in origin)
+    gx, gy, gz = (int(size),) * 3 if extents is None else (int(v) for v in extents)
+    if min(ox, oy, oz, gx, gy, gz) < 0:
+        raise ValueError("list_voxels: origin and extents are unsigned")
+    return ox, oy, oz, gx, gy, gz
+
+
+def _list_voxels(image, origin, extents, capacity):
+    """vhx_flat_list_voxels of a FlatTree or TreeImage."""
+    q = N.PointsOut(*_list_box(image.boxtree_size, origin, extents))
+    n = ctypes.c_uint64()
+    q.count = ctypes.pointer(n)
+    if capacity is None:  # size the arrays from a count-only call
+        _tree_check(N.lib().vhx_flat_list_voxels(ctypes.byref(image.desc), ctypes.byref(q)), "list_voxels")
+        cap = n.value
+    else:
+        cap = int(capacity)
+        if cap < 0:
+            raise ValueError("list_voxels: capacity is unsigned")
+    pos, alb, dat = np.empty((cap, 3), np.uint32), np.empty(cap, np.uint32), np.empty(cap, np.uint32)
+    q.capacity, q.positions, q.albedo, q.data = cap, pos.ctypes.data, alb.ctypes.data, dat.ctypes.data
+    _tree_check(N.lib().vhx_flat_list_voxels(ctypes.byref(image.desc), ctypes.byref(q)), "list_voxels")
+    k = min(n.value, cap)
+    if capacity is None:
+        return pos[:k], alb[:k], dat[:k]
+    return pos[:k], alb[:k], dat[:k], n.value
+
+
+_LIST_DOC = """vhx_flat_list_voxels: the occupied voxels of the box at `origin` (x, y, z) with `extents` (gx, gy, gz; None =
+        the whole root cube) as (positions (n, 3), albedo (n,), data (n,)), uint32 arrays -- what Raytracer.list_voxels
+        gives for this image on the device, bit for bit. A voxel is listed when read_dense(data=True) gives it a colour or
+        a data value, in the positional order include/vhx.h states. capacity=None sizes the arrays from a count-only
+        call; with an explicit capacity the first min(count, capacity) entries come back, and count as a fourth item."""
+
+
 class TreeImage:
     """A flattened tree held in numpy arrays (Raytracer.download): the seven arrays and counts of a vhx_tree_desc,
     under FlatTree's names; `desc` points into them, so the image uploads, traces on the oracle and saves like one."""
+
+    def list_voxels(self, origin=(0, 0, 0), extents=None, capacity=None):
+        return _list_voxels(self, origin, extents, capacity)
+
+    list_voxels.__doc__ = _LIST_DOC
+
+    def count_voxels(self, origin=(0, 0, 0), extents=None):
+        """The number of voxels list_voxels lists for the box (a count-only call)."""
+        return _list_voxels(self, origin, extents, 0)[3]
 
     def palette_compacted(self):
         """vhx_flat_compact_palette: this image with the colour palette the builders give the voxels it holds now, as a
@@ -420,6 +466,15 @@ class FlatTree:
         """vhx_flat_compact_palette (see TreeImage.palette_compacted): a freshly built image, plain or simplified, comes
         back equal to itself."""
         return _palette_compacted(self)
+
+    def list_voxels(self, origin=(0, 0, 0), extents=None, capacity=None):
+        return _list_voxels(self, origin, extents, capacity)
+
+    list_voxels.__doc__ = _LIST_DOC
+
+    def count_voxels(self, origin=(0, 0, 0), extents=None):
+        """The number of voxels list_voxels lists for the box (a count-only call)."""
+        return _list_voxels(self, origin, extents, 0)[3]
 
     @classmethod
     def _from_handle(cls, h):

@@ -1,7 +1,7 @@
 // The pieces of the dense build (vhx_build.hip) that the in-place dense write (vhx_edit.hip) uses as well: the colour
 // table with its insert, lookup, compaction and ranking, the scans over occupancy words, and the counters read back.
 // The compaction (vhx_compact.hip) uses the scans; the simplification (vhx_simplify.hip) the scans and the table, for
-// the distinct Solid values.
+// the distinct Solid values; the listing (vhx_list.hip) the scans whose element count stays on the device.
 // Each unit that includes this gets its own copy of the kernels (anonymous namespace).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -168,6 +168,59 @@ __global__ __launch_bounds__(256) void k_scan_apply(const u64 *occ, uint64_t n, 
     u64 s = 0;
     for (uint32_t i = 0; i < SCAN_ITEMS; ++i) {
         v[i] = base + i < n ? scan_value<MODE>(occ[base + i], root != 0) : 0u;
+        s += v[i];
+    }
+    u64 run = part[blockIdx.x] + block_scan(s, lds) - s;
+    for (uint32_t i = 0; i < SCAN_ITEMS; ++i) {
+        if (base + i < n) out[base + i] = run;
+        run += v[i];
+    }
+}
+
+// ---- the same three scans over the first min(*n_dev, cap) words, for a caller whose element count stays on the device
+// (vhx_list.hip): the launches are sized by cap, and the blocks past the count leave at once
+template <int MODE>
+__global__ __launch_bounds__(256) void k_dscan_sums(const u64 *in, const u64 *n_dev, u64 cap, u64 *part) {
+    __shared__ u64 lds[4];
+    const u64 n = min(*n_dev, cap);
+    if ((u64)blockIdx.x * SCAN_TILE >= n) return;  // the whole block
+    const u64 base = (u64)blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
+    u64 s = 0;
+    for (uint32_t i = 0; i < SCAN_ITEMS; ++i)
+        if (base + i < n) s += scan_value<MODE>(in[base + i], false);
+    s = block_scan(s, lds);
+    if (threadIdx.x == 255) part[blockIdx.x] = s;
+}
+
+[[maybe_unused]] __global__ __launch_bounds__(256) void k_dscan_top(u64 *part, const u64 *n_dev, u64 cap, u64 *total) {
+    __shared__ u64 lds[4];
+    __shared__ u64 carry;
+    const u64 nb = (min(*n_dev, cap) + SCAN_TILE - 1) / SCAN_TILE;
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    for (u64 c0 = 0; c0 < nb; c0 += 256) {
+        const u64 i = c0 + threadIdx.x;
+        const u64 v = i < nb ? part[i] : 0;
+        const u64 incl = block_scan(v, lds);
+        if (i < nb) part[i] = carry + incl - v;
+        __syncthreads();
+        if (threadIdx.x == 255) carry += incl;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+
+// out may be in: a thread reads its own words before it writes them
+template <int MODE>
+__global__ __launch_bounds__(256) void k_dscan_apply(const u64 *in, const u64 *n_dev, u64 cap, const u64 *part, u64 *out) {
+    __shared__ u64 lds[4];
+    const u64 n = min(*n_dev, cap);
+    if ((u64)blockIdx.x * SCAN_TILE >= n) return;  // the whole block
+    const u64 base = (u64)blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
+    uint32_t v[SCAN_ITEMS];
+    u64 s = 0;
+    for (uint32_t i = 0; i < SCAN_ITEMS; ++i) {
+        v[i] = base + i < n ? scan_value<MODE>(in[base + i], false) : 0u;
         s += v[i];
     }
     u64 run = part[blockIdx.x] + block_scan(s, lds) - s;

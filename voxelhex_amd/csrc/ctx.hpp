@@ -1,6 +1,6 @@
 // Internal context of libvhx, shared by the translation units of the device side: vhx_device.hip (tracing), vhx_tree.hip
 // (the device tree), vhx_ctx.hip (contexts, ordering, settings), vhx_mgpu.hip, vhx_build.hip, vhx_query.hip,
-// vhx_edit.hip, vhx_points.hip, vhx_compact.hip, vhx_simplify.hip and vhx_palette.hip.
+// vhx_edit.hip, vhx_points.hip, vhx_compact.hip, vhx_simplify.hip, vhx_palette.hip and vhx_list.hip.
 // Not part of the ABI: callers see vhx_ctx only as an opaque pointer (include/vhx.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -175,6 +175,13 @@ struct vhx_ctx {
     struct PaletteScratch {
         DevBuf org, first, map, ctl;
     } palette;
+    // vhx_list_voxels (vhx_list.hip): the frontier of the descent (two lists of nodes with their origins, ping-pong),
+    // per frontier node the mask of its surviving sectants and the place of its first child, the brick-sized units under
+    // the box with their voxel counts (scanned in place into their first ranks), the scans' block sums, the counters
+    // read back, and the staging of host arrays. Bounded by the nodes and leaf sectants under the box
+    struct ListScratch {
+        DevBuf fr[2], mask, first, unit, ucnt, part, ctl, out;
+    } list;
     // depth-prepass mode (vhx_set_depth_prepass; opt-in, not the reference path)
     bool prepass = false, in_prepass = false;
     // fused hard shadows (vhx_set_shadow_light): each hit's shadow ray traced in the lane that finished its primary ray

@@ -765,6 +765,125 @@ static int palette_image(const vhx_tree_desc &t, vhx_flat **out) {
     return VHX_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- vhx_flat_list_voxels
+// The plain walk of vhx_list_voxels (include/vhx.h): depth-first, sectants ascending, cells in flat order, clipped to the
+// box. Run once to count and to find a refusal, then once more to write, so that a refused call writes nothing.
+namespace {
+struct ListWalk {
+    const vhx_tree_desc &t;
+    const vhx_points_out &q;
+    uint32_t lg_bd = 0, levels = 0;
+    bool write = false, bad = false;
+    uint64_t total = 0;
+
+    bool meets(uint32_t x, uint32_t y, uint32_t z, uint32_t edge) const {
+        return x < q.ox + q.gx && x + edge > q.ox && y < q.oy + q.gy && y + edge > q.oy && z < q.oz + q.gz &&
+               z + edge > q.oz;
+    }
+    uint32_t albedo_of(uint32_t v) const {
+        const uint32_t ci = v & 0xFFFFu;
+        if (ci == 0xFFFFu || ci >= t.color_count || !t.color_palette) return 0u;
+        const uint32_t a = t.color_palette[ci];
+        return (a >> 24) != 0u ? a : 0u;
+    }
+    uint32_t data_of(uint32_t v) const {
+        const uint32_t di = v >> 16;
+        if (v == VHX_EMPTY || di == 0xFFFFu || di >= t.data_count || !t.data_palette) return 0u;
+        return t.data_palette[di];
+    }
+    // the cells of the brick-sized cube at (X, Y, Z), sectant s of the smallest leaf `node`
+    void unit(uint32_t node, bool uniform, uint32_t s, uint32_t X, uint32_t Y, uint32_t Z) {
+        const uint32_t bd = t.brick_dim, m = bd - 1u;
+        const uint32_t desc = t.node_children[(uint64_t)node * 64u + (uniform ? 0u : s)];
+        if (desc == VHX_EMPTY) return;
+        const bool solid = (desc & VHX_SOLID_BIT) != 0u;
+        uint32_t sv = VHX_EMPTY;
+        if (solid) {
+            const uint32_t i = desc & 0x7FFFFFFFu;
+            if (i < t.solid_count && t.solid_values) sv = t.solid_values[i];
+        } else if (desc >= t.brick_count || !t.voxels) {
+            return;
+        }
+        const uint32_t *brick = solid ? nullptr : t.voxels + ((uint64_t)desc << (3u * lg_bd));
+        for (uint32_t flat = 0; flat < bd * bd * bd; ++flat) {
+            const uint32_t cx = flat & m, cy = (flat >> lg_bd) & m, cz = flat >> (2u * lg_bd);
+            const uint32_t x = X + cx, y = Y + cy, z = Z + cz;
+            if (x - q.ox >= q.gx || y - q.oy >= q.gy || z - q.oz >= q.gz) continue;
+            uint32_t v = sv;
+            if (!solid) {
+                if (uniform) {  // the brick spans the leaf: a cell is 4 voxels wide, and comes back raw
+                    const uint32_t um = 4u * bd - 1u;
+                    v = brick[((x & um) >> 2) + ((((y & um) >> 2) + (((z & um) >> 2) << lg_bd)) << lg_bd)];
+                } else {
+                    v = brick[flat];
+                }
+            }
+            const uint32_t a = albedo_of(v), d = data_of(v);
+            if (a == 0u && d == 0u) continue;
+            if (write && total < q.capacity) {
+                if (q.positions) {
+                    q.positions[3 * total] = x;
+                    q.positions[3 * total + 1] = y;
+                    q.positions[3 * total + 2] = z;
+                }
+                if (q.albedo) q.albedo[total] = a;
+                if (q.data) q.data[total] = d;
+            }
+            ++total;
+        }
+    }
+    void walk(uint32_t node, uint32_t lvl, uint32_t X, uint32_t Y, uint32_t Z, uint32_t lg) {
+        const uint32_t type = t.node_type[node], edge = 1u << (lg - 2u);
+        if (type != VHX_NODE_INTERNAL && type != VHX_NODE_LEAF && type != VHX_NODE_UNIFORM_LEAF) return;
+        if (type != VHX_NODE_INTERNAL && lvl + 1u != levels) {  // a brick stretched over a larger cube
+            bad = true;
+            return;
+        }
+        if (type == VHX_NODE_INTERNAL && lvl + 1u >= levels) return;  // no node is smaller than 4 * brick_dim
+        for (uint32_t s = 0; s < 64u && !bad; ++s) {
+            const uint32_t x = X + (s & 3u) * edge, y = Y + ((s >> 2) & 3u) * edge, z = Z + (s >> 4) * edge;
+            if (!meets(x, y, z, edge)) continue;
+            if (type == VHX_NODE_INTERNAL) {
+                const uint32_t e = t.node_children[(uint64_t)node * 64u + s];
+                if (e != VHX_EMPTY && e < t.node_count) walk(e, lvl + 1u, x, y, z, lg - 2u);
+            } else {
+                unit(node, type == VHX_NODE_UNIFORM_LEAF, s, x, y, z);
+            }
+        }
+    }
+};
+}  // namespace
+
+static int list_image(const vhx_tree_desc &t, const vhx_points_out &q) {
+    const uint32_t S = t.boxtree_size, bd = t.brick_dim;
+    if (!t.node_type || !t.node_children || t.node_count == 0) return VHX_E_INVALID_ARG;
+    uint32_t lg_size = 0, lg_bd = 0;
+    while (lg_size < 31u && (1u << lg_size) < S) ++lg_size;
+    while (lg_bd < 31u && (1u << lg_bd) < bd) ++lg_bd;
+    if (S == 0 || bd == 0 || (1u << lg_size) != S || (1u << lg_bd) != bd || lg_size < lg_bd + 2u ||
+        ((lg_size - lg_bd) & 1u))
+        return VHX_E_INVALID_ARG;
+    if (q.gx == 0 || q.gy == 0 || q.gz == 0 || (uint64_t)q.ox + q.gx > S || (uint64_t)q.oy + q.gy > S ||
+        (uint64_t)q.oz + q.gz > S)
+        return VHX_E_INVALID_ARG;
+    const uint64_t lim = 1ull << 48, gxy = (uint64_t)q.gx * q.gy;
+    if (gxy >= lim || q.gz > (lim - 1u) / gxy) return VHX_E_CAPACITY;
+    if (lg_bd > 10u) return VHX_E_CAPACITY;  // a brick's cells are counted in 32 bits
+    ListWalk w{t, q};
+    w.lg_bd = lg_bd;
+    w.levels = (lg_size - lg_bd) / 2u;
+    w.walk(0, 0, 0, 0, 0, lg_size);
+    if (w.bad) return VHX_E_STATE;
+    const uint64_t total = w.total;
+    if (q.capacity > 0 && total > 0 && (q.positions || q.albedo || q.data)) {
+        w.write = true;
+        w.total = 0;
+        w.walk(0, 0, 0, 0, 0, lg_size);
+    }
+    *q.count = total;
+    return VHX_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- C ABI
 extern "C" {
 
@@ -1043,6 +1162,10 @@ int vhx_flat_compact_palette(const vhx_tree_desc *tree, vhx_flat **out) {
     } catch (const std::bad_alloc &) {
         return VHX_E_CAPACITY;
     }
+}
+int vhx_flat_list_voxels(const vhx_tree_desc *tree, const vhx_points_out *q) {
+    if (!tree || !q || !q->count) return VHX_E_INVALID_ARG;
+    return list_image(*tree, *q);
 }
 int vhx_flat_simplify(const vhx_tree_desc *tree, vhx_flat **out) {
     if (!out) return VHX_E_INVALID_ARG;

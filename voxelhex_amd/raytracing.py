@@ -536,6 +536,58 @@ class Raytracer:
         """vhx_set_voxels without values: every listed voxel is cleared (the batched BoxTree.clear)."""
         self.set_voxels(positions, 0, 0, "replace")
 
+    def _list_query(self, origin, extents):
+        from .boxtree import _list_box
+        size = self.tree_counts().boxtree_size if extents is None else 0
+        q = N.PointsOut(*_list_box(size, origin, extents))
+        n = ctypes.c_uint64()
+        q.count = ctypes.pointer(n)
+        return q, n
+
+    def count_voxels(self, origin=(0, 0, 0), extents=None):
+        """vhx_list_voxels with capacity 0: the number of voxels of the box at `origin` (x, y, z) with `extents` (gx, gy,
+        gz; None = the whole root cube) that list_voxels would list."""
+        q, n = self._list_query(origin, extents)
+        self._check(N.lib().vhx_list_voxels(self._h, ctypes.byref(q), 0))
+        return n.value
+
+    def list_voxels(self, origin=(0, 0, 0), extents=None, capacity=None, device=False):
+        """vhx_list_voxels: the occupied voxels of the box at `origin` (x, y, z) with `extents` (gx, gy, gz; None = the
+        whole root cube) as (positions (n, 3), albedo (n,), data (n,)) -- the sparse form of read_dense(data=True) and
+        the inverse of set_voxels. A voxel is listed when read_dense(data=True) gives it a colour or a data value, with
+        those two words; the order is positional (sectant digits from the root down, then the flat cell index:
+        include/vhx.h), so it does not depend on how the tree is structured. device=False gives uint32 numpy arrays,
+        device=True int32 torch tensors on this context's device, complete when the call returns. capacity=None sizes
+        the arrays from a count-only call first; with an explicit capacity the first min(count, capacity) entries come
+        back, and count as a fourth item. Allowed on shared contexts; cost and scratch follow the nodes and bricks under
+        the box, not its volume."""
+        q, n = self._list_query(origin, extents)
+        if capacity is None:
+            self._check(N.lib().vhx_list_voxels(self._h, ctypes.byref(q), 0))
+            cap = n.value
+        else:
+            cap = int(capacity)
+            if cap < 0:
+                raise ValueError("list_voxels: capacity is unsigned")
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            pos = torch.empty((cap, 3), dtype=torch.int32, device=dev)
+            alb = torch.empty(cap, dtype=torch.int32, device=dev)
+            dat = torch.empty(cap, dtype=torch.int32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            q.positions, q.albedo, q.data = pos.data_ptr(), alb.data_ptr(), dat.data_ptr()
+        else:
+            pos, alb, dat = np.empty((cap, 3), np.uint32), np.empty(cap, np.uint32), np.empty(cap, np.uint32)
+            q.positions, q.albedo, q.data = pos.ctypes.data, alb.ctypes.data, dat.ctypes.data
+        q.capacity = cap
+        if cap or capacity is not None:
+            self._check(N.lib().vhx_list_voxels(self._h, ctypes.byref(q), 1 if device else 0))
+        k = min(n.value, cap)
+        if capacity is None:
+            return pos[:k], alb[:k], dat[:k]
+        return pos[:k], alb[:k], dat[:k], n.value
+
     def orphans(self):
         """vhx_tree_orphans: (nodes, bricks) that write_dense / fill_box unlinked since the last upload or build; their
         slots are not reused (compact() drops them)."""
