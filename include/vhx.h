@@ -337,7 +337,8 @@ typedef struct vhx_dense_in {
  * not of canonical depth (a LOD-cut or streamed view); VHX_E_CAPACITY past 65,535 colours, 2^31 bricks or 2^28 touched
  * leaf cubes; VHX_E_INVALID_ARG for a bad box or mode. On a tree with data values the call behaves as described (cells
  * outside the box keep their data halves), and the "bit for bit a fresh build" closure with vhx_simplify_tree /
- * vhx_compact_tree and vhx_compact_palette holds for such a tree up to the order of data_palette. */
+ * vhx_compact_tree holds for such a tree, in all seven buffers, with vhx_compact_palettes in place of
+ * vhx_compact_palette. */
 int vhx_write_dense(vhx_ctx *ctx, const vhx_dense_in *box, int on_device);
 /* vhx_write_dense with user data. Every voxel of the box has an albedo word a (box->albedo, or box->fill where that is
  * NULL) and a data word d (`data`, a plane with the extents and indexing of box->albedo that lives where it lives, or
@@ -461,7 +462,7 @@ int vhx_compact_tree(vhx_ctx *ctx, uint32_t *nodes_dropped, uint32_t *bricks_dro
  * value points to empty without being VHX_EMPTY, which may now read raw (under a UniformLeaf) or empty, as described
  * for those node kinds above. Traces are those of the new image: a hit in a Solid brick reports the brick's cube, no
  * cell, and an impact computed on that cube. On a tree with data values the call behaves the same (a brick is Solid
- * where its cells are one value in both halves), and the closure above holds up to the order of data_palette as well.
+ * where its cells are one value in both halves), and vhx_compact_palettes after it closes the caveat for both palettes.
  * Contract as vhx_compact_tree: out of place through new buffers at the new counts (peak device memory the old tree
  * plus the new one), nothing of the old tree written, a refused call or a failed allocation leaves it bit for bit as it
  * was; owner context only (VHX_E_STATE on a shared one); frames submitted before it trace the old buffers, frames after
@@ -490,8 +491,8 @@ int vhx_simplify_tree(vhx_ctx *ctx, uint32_t *nodes_dropped, uint32_t *bricks_dr
  * vhx_simplify_tree and this call leave exactly the image vhx_build_tree_dense_simplified gives for the same voxels,
  * vhx_compact_tree and this call the image of vhx_build_tree_dense, and a palette that an editing session has filled
  * with colours no voxel holds any more (VHX_E_CAPACITY from vhx_write_dense) has room again. On a tree with data
- * values the call behaves the same, and "exactly the image of the build" holds up to the order of data_palette, which no
- * call canonicalises.
+ * values the call behaves the same and leaves data_palette alone; vhx_compact_palettes (below) canonicalises it as well,
+ * and "exactly the image of the build" then holds for such a tree in all seven buffers.
  * The tree is only read until the one readback of the counters, so a refused call leaves it bit for bit as it was:
  * VHX_E_STATE before any upload, on a shared context, while node MIPs are set (MIP bricks are not reachable through
  * the entries, their colours would be dropped), and for a malformed tree (vhx_compact_tree's cases, a Solid entry at
@@ -501,6 +502,30 @@ int vhx_simplify_tree(vhx_ctx *ctx, uint32_t *nodes_dropped, uint32_t *bricks_dr
  * time of its rewrite pass (the one read and write of the voxel buffer) in place of a trace's.
  * A streamed view's host cache (vhx_stream.h) keeps palette indices: the caller must not call this under it. */
 int vhx_compact_palette(vhx_ctx *ctx, uint32_t *colors_dropped);
+/* The halves of a value that vhx_compact_palettes and vhx_flat_compact_palettes (vhx_boxtree.h) rewrite: a bit mask. */
+#define VHX_PALETTE_COLOR 1u
+#define VHX_PALETTE_DATA 2u
+/* vhx_compact_palette for the halves selected by `which` (a mask of VHX_PALETTE_COLOR and VHX_PALETTE_DATA), in one
+ * walk and one pass over the voxel buffer: afterwards color_palette and / or data_palette are the builders' palettes
+ * (vhx_build_tree_dense_data) of the voxels the tree holds now -- the image of vhx_flat_compact_palettes (vhx_boxtree.h,
+ * which states the rules) of the tree, bit for bit. The data rule is the colour rule with "the entry is not 0" in place
+ * of "the alpha byte is not 0": data values no reachable value names leave data_palette, entries holding the same value
+ * become one, and the values that stay are ordered by the first index of the cubes that hold them. Every cell of every
+ * brick slot (orphaned ones included) and every entry of solid_values becomes map[v & 0xFFFF] | dmap[v >> 16] << 16
+ * with both halves selected, and has only the selected half translated otherwise; a half that is not selected and its
+ * palette are untouched. With which == VHX_PALETTE_COLOR the call is vhx_compact_palette, bit for bit. color_count and
+ * data_count become the numbers of used entries; *colors_dropped and *data_dropped (either may be NULL) receive the old
+ * count minus the new, 0 for a half that is not selected. Everything else is vhx_compact_palette's: buffers are not
+ * reallocated, vhx_read_dense and vhx_read_dense_data of any box and every trace field but `value` are unchanged, and
+ * `value` is the old one through the maps. So after any series of vhx_write_dense_data, vhx_set_voxels and
+ * vhx_write_dense calls, vhx_simplify_tree and this call leave exactly the image vhx_dense_build_data(simplified = 1)
+ * gives for the same voxels, in all seven buffers, vhx_compact_tree and this call that of vhx_build_tree_dense_data; and
+ * a data_palette that a session has filled with ids no voxel holds any more (VHX_E_CAPACITY from the write calls) has
+ * room again.
+ * Refusals and ordering as vhx_compact_palette, with the tree only read until the one readback of the counters (a
+ * refused call leaves it bit for bit as it was), and VHX_E_INVALID_ARG for which == 0 or a bit outside the two. A
+ * vhx_sync after the call reports the device time of its rewrite pass. */
+int vhx_compact_palettes(vhx_ctx *ctx, uint32_t which, uint32_t *colors_dropped, uint32_t *data_dropped);
 
 /* Tracing --------------------------------------------------------------------------------------------------- */
 /* Traces primary rays for every pixel of the square tiles k = tile_start, tile_start+tile_stride, ... (raster order

@@ -30,6 +30,7 @@
  *   vhx_flat_simplify          <- that image after BoxTree::simplify(ROOT, recursive), as insert / clear leave a tree
  *                                 with auto-simplify on
  *   vhx_flat_compact_palette   <- no reference counterpart: an edited image with the colour palette of a fresh build
+ *   vhx_flat_compact_palettes  <- the same for the selected halves: the colour palette, the data palette or both
  *   vhx_flat_list_voxels       <- no single counterpart (BoxTree::get iterated over a box): its occupied voxels as a list
  *
  * Tree type parameter: T = u32 (the reference default, BoxTree<T = u32>, src/boxtree/types.rs:219).
@@ -240,6 +241,24 @@ int vhx_flat_simplify(const vhx_tree_desc *tree, vhx_flat **out);
  * UniformLeaf so deep that a cell of its bricks would be smaller than a voxel (its cubes would have no corner of their
  * own). Duplicate palette entries are accepted. Node MIPs are not carried over. */
 int vhx_flat_compact_palette(const vhx_tree_desc *tree, vhx_flat **out);
+/* The image `tree` with canonical palettes for the halves selected by `which`, a mask of VHX_PALETTE_COLOR and
+ * VHX_PALETTE_DATA (vhx.h): the CPU counterpart of vhx_compact_palettes (vhx.h), bit for bit. With which ==
+ * VHX_PALETTE_COLOR the result is vhx_flat_compact_palette's. The data rule is the colour rule above with the data half
+ * of points_to_empty in place of the colour half:
+ *   A reachable value v names a data value when di = v >> 16 is not 0xFFFF, di < data_count and data_palette[di] is not
+ *     0. Reachability, the cubes on which values sit and the first index of a cube's min corner, (x * boxtree_size +
+ *     y) * boxtree_size + z, are those of the colour rule. Entries holding the same 32-bit value are one value.
+ *   The new data_palette holds the used values in increasing first index; data_count is their number.
+ *   dmap[di] is the new index of the value of entry di, and 0xFFFF where the entry is 0 or unused and for every di that
+ *     names nothing.
+ *   Every cell of every brick slot [0, brick_count), orphaned ones included, and every entry of solid_values is
+ *     rewritten: with both halves selected to map[v & 0xFFFF] | dmap[v >> 16] << 16, with one half selected with only
+ *     that half translated. VHX_EMPTY stays VHX_EMPTY, and a value that pointed to empty still does. solid_values is
+ *     translated, never deduplicated or reordered. The palette of a half that is not selected stays as it is.
+ * The image of a dense build with data (vhx_dense_build_data), plain or simplified, is returned as it is, and the
+ * function is idempotent.
+ * Errors as vhx_flat_compact_palette, and VHX_E_INVALID_ARG for which == 0 or a bit outside the two. */
+int vhx_flat_compact_palettes(const vhx_tree_desc *tree, uint32_t which, vhx_flat **out);
 /* vhx_list_voxels (vhx.h, which states the contract) over the host image `tree`, with host arrays: the CPU counterpart
  * of the device call, bit for bit in *count and in every array. It is the plain walk -- depth-first from node 0, sectants
  * ascending, the cells of a brick in flat order, clipped to the box -- with a voxel's two words computed as

@@ -47,6 +47,7 @@ VHX_BUF_NODE_TYPE, VHX_BUF_NODE_OCBITS, VHX_BUF_NODE_CHILDREN, VHX_BUF_VOXELS = 
 VHX_BUF_SOLID_VALUES, VHX_BUF_COLOR_PALETTE, VHX_BUF_DATA_PALETTE = 4, 5, 6
 VHX_DERIVED_NODE_HDR, VHX_DERIVED_BRICK_OCC = 0, 1
 VHX_WRITE_REPLACE, VHX_WRITE_INSERT = 0, 1
+VHX_PALETTE_COLOR, VHX_PALETTE_DATA = 1, 2
 
 
 class TreeDesc(ctypes.Structure):
@@ -150,6 +151,7 @@ SIGNATURES = [
     ("vhx_compact_tree", c_int, [c_void_p, P(c_u32), P(c_u32)]),
     ("vhx_simplify_tree", c_int, [c_void_p, P(c_u32), P(c_u32)]),
     ("vhx_compact_palette", c_int, [c_void_p, P(c_u32)]),
+    ("vhx_compact_palettes", c_int, [c_void_p, c_u32, P(c_u32), P(c_u32)]),
     ("vhx_set_node_mips", c_int, [c_void_p, c_void_p, c_u32]),
     ("vhx_update_range", c_int, [c_void_p, c_int, c_u64, c_u64, c_void_p]),
     ("vhx_update_ranges", c_int, [c_void_p, c_void_p, c_u32]),
@@ -228,6 +230,7 @@ SIGNATURES = [
     ("vhx_flat_compact", c_int, [P(TreeDesc), P(c_void_p)]),
     ("vhx_flat_simplify", c_int, [P(TreeDesc), P(c_void_p)]),
     ("vhx_flat_compact_palette", c_int, [P(TreeDesc), P(c_void_p)]),
+    ("vhx_flat_compact_palettes", c_int, [P(TreeDesc), c_u32, P(c_void_p)]),
     ("vhx_flat_list_voxels", c_int, [P(TreeDesc), P(PointsOut)]),
     ("vhx_boxtree_switch_mips", c_int, [c_void_p, c_int]),
     ("vhx_boxtree_set_mip_method", c_int, [c_void_p, c_u32, c_u32, c_f32]),

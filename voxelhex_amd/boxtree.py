@@ -310,6 +310,22 @@ def _palette_compacted(image):
     return FlatTree(h.value)
 
 
+def _palettes_mask(color, data):
+    """The `which` mask of the palette calls; at least one half must be selected."""
+    which = (N.VHX_PALETTE_COLOR if color else 0) | (N.VHX_PALETTE_DATA if data else 0)
+    if which == 0:
+        raise ValueError("compact_palettes: select the colour half, the data half or both")
+    return which
+
+
+def _palettes_compacted(image, color, data):
+    """vhx_flat_compact_palettes of a FlatTree or TreeImage, as a new FlatTree."""
+    h = ctypes.c_void_p()
+    _tree_check(N.lib().vhx_flat_compact_palettes(ctypes.byref(image.desc), _palettes_mask(color, data),
+                                                  ctypes.byref(h)), "palettes_compacted: a malformed image")
+    return FlatTree(h.value)
+
+
 def _list_box(size, origin, extents):
     """(ox, oy, oz, gx, gy, gz) of a list / count call; extents None = the whole root cube."""
     ox, oy, oz = (int(v) for v in origin)
@@ -367,6 +383,14 @@ class TreeImage:
         outer, y, z inner); the colour half of every cell (orphaned slots included) and solid value is translated, and
         nothing else changes (include/vhx_boxtree.h states every rule). InvalidStructure for a malformed image."""
         return _palette_compacted(self)
+
+    def palettes_compacted(self, color=True, data=True):
+        """vhx_flat_compact_palettes: palette_compacted for the selected halves -- with data=True data_palette too
+        becomes the builders' palette of the voxels the image holds now (values no reachable value names leave, equal
+        entries merge, the rest in first-appearance order) and the data half of every cell and solid value is
+        translated; a half that is not selected and its palette stay. What Raytracer.compact_palettes leaves on the
+        device, bit for bit; color=True, data=False is palette_compacted()."""
+        return _palettes_compacted(self, color, data)
 
     def compacted(self):
         """vhx_flat_compact: this image without its unreachable node and brick slots, renumbered as the builders number
@@ -466,6 +490,11 @@ class FlatTree:
         """vhx_flat_compact_palette (see TreeImage.palette_compacted): a freshly built image, plain or simplified, comes
         back equal to itself."""
         return _palette_compacted(self)
+
+    def palettes_compacted(self, color=True, data=True):
+        """vhx_flat_compact_palettes (see TreeImage.palettes_compacted): a freshly built image with data, plain or
+        simplified, comes back as it is."""
+        return _palettes_compacted(self, color, data)
 
     def list_voxels(self, origin=(0, 0, 0), extents=None, capacity=None):
         return _list_voxels(self, origin, extents, capacity)

@@ -169,11 +169,12 @@ struct vhx_ctx {
     struct SimplifyScratch {
         DevBuf binfo, pmask, gmask, bfirst, ent, bsrc, newb, ctl;
     } simplify;
-    // vhx_compact_palette (vhx_palette.hip): per new node its origin and level, per palette index the smallest first
-    // index of a reachable value that names it and its new index, and the counters read back. Reset by each call; the
-    // node maps are the compaction's, the colour table and the scans' block sums the build's
+    // vhx_compact_palette(s) (vhx_palette.hip): per new node its origin and level, per palette index the smallest first
+    // index of a reachable value that names it and its new index, and the counters read back; dfirst and dmap are the
+    // same two arrays for data_palette. Reset by each call; the node maps are the compaction's, the colour table, the
+    // data table (build.dtable) and the scans' block sums the build's
     struct PaletteScratch {
-        DevBuf org, first, map, ctl;
+        DevBuf org, first, map, ctl, dfirst, dmap;
     } palette;
     // vhx_list_voxels (vhx_list.hip): the frontier of the descent (two lists of nodes with their origins, ping-pong),
     // per frontier node the mask of its surviving sectants and the place of its first child, the brick-sized units under

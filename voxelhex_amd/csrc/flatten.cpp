@@ -662,21 +662,24 @@ static int compact_image(const vhx_tree_desc &t, vhx_flat **out) {
 }
 
 // ---------------------------------------------------------------------------------------------- palette
-// The image with the colour palette the builders give the voxels it holds now (include/vhx_boxtree.h
-// states the rules): the used colours by the first index of the cubes that hold them, every cell and solid value
-// translated, nothing else touched. The CPU reference of vhx_compact_palette.
-static int palette_image(const vhx_tree_desc &t, vhx_flat **out) {
+// The image with the palettes the builders give the voxels it holds now (include/vhx_boxtree.h
+// states the rules): per selected half (VHX_PALETTE_COLOR, VHX_PALETTE_DATA) the used entries by the first index of the
+// cubes that hold them, every cell and solid value translated, nothing else touched. One walk serves both halves. The
+// CPU reference of vhx_compact_palettes (and, with the colour half alone, of vhx_compact_palette).
+static int palettes_image(const vhx_tree_desc &t, uint32_t which, vhx_flat **out) {
     const uint32_t nn = t.node_count, nb = t.brick_count, bd = t.brick_dim;
     const uint64_t n3 = (uint64_t)bd * bd * bd, S = t.boxtree_size;
     if (nn == 0 || n3 == 0 || !t.node_type || !t.node_ocbits || !t.node_children || (nb && !t.voxels) ||
         (t.solid_count && !t.solid_values) || (t.color_count && !t.color_palette) || (t.data_count && !t.data_palette))
         return VHX_E_INVALID_ARG;
-    const uint32_t ncol = std::min<uint32_t>(t.color_count, 0xFFFFu);  // what a 16-bit index can name
-    std::vector<uint64_t> first(0x10000, ~0ull);  // per palette entry: the smallest first index of a value naming it
+    const bool do_color = (which & VHX_PALETTE_COLOR) != 0, do_data = (which & VHX_PALETTE_DATA) != 0;
+    // per palette entry of a half: the smallest first index of a value naming it
+    std::vector<uint64_t> first(do_color ? 0x10000 : 0, ~0ull), dfirst(do_data ? 0x10000 : 0, ~0ull);
     auto see = [&](uint32_t v, uint64_t x, uint64_t y, uint64_t z) {
-        const uint32_t ci = v & 0xFFFFu;
-        if (ci == 0xFFFFu) return;
-        first[ci] = std::min(first[ci], (x * S + y) * S + z);
+        const uint32_t ci = v & 0xFFFFu, di = v >> 16;
+        const uint64_t idx = (x * S + y) * S + z;
+        if (do_color && ci != 0xFFFFu) first[ci] = std::min(first[ci], idx);
+        if (do_data && di != 0xFFFFu) dfirst[di] = std::min(dfirst[di], idx);
     };
     struct At {
         uint32_t node, level;
@@ -723,30 +726,48 @@ static int palette_image(const vhx_tree_desc &t, vhx_flat **out) {
                     for (uint32_t cx = 0; cx < bd; ++cx, ++c) see(cells[c], bx + cx * cell, by + cy * cell, bz + cz * cell);
         }
     }
-    // entries of one colour are one colour; an entry of alpha 0 names none
-    std::unordered_map<uint32_t, uint64_t> colour_first;
-    for (uint32_t ci = 0; ci < ncol; ++ci) {
-        const uint32_t col = t.color_palette[ci];
-        if (first[ci] == ~0ull || (col >> 24) == 0) continue;
-        auto it = colour_first.emplace(col, first[ci]).first;
-        it->second = std::min(it->second, first[ci]);
-    }
-    std::vector<std::pair<uint64_t, uint32_t>> ranked;
-    ranked.reserve(colour_first.size());
-    for (const auto &kv : colour_first) ranked.emplace_back(kv.second, kv.first);
-    std::sort(ranked.begin(), ranked.end());
-    std::unordered_map<uint32_t, uint32_t> index_of;
-    for (size_t r = 0; r < ranked.size(); ++r) index_of[ranked[r].second] = (uint32_t)r;
-    std::vector<uint32_t> map(0x10000, 0xFFFFu);
-    for (uint32_t ci = 0; ci < ncol; ++ci) {
-        const uint32_t col = t.color_palette[ci];
-        if ((col >> 24) == 0) continue;
-        const auto it = index_of.find(col);
-        if (it != index_of.end()) map[ci] = it->second;
-    }
-    auto mapped = [&](uint32_t v) { return (v & 0xFFFF0000u) | map[v & 0xFFFFu]; };
-
+    // One half: entries of one value are one value; an entry the half's test rejects (alpha 0, the value 0) names none.
+    // Leaves the new palette in `pal` and the map old index -> new index, 0xFFFF where the entry names nothing
+    auto settle = [](const uint32_t *old, uint32_t count, const std::vector<uint64_t> &fst, bool data,
+                     std::vector<uint32_t> &pal, std::vector<uint32_t> &map) {
+        const uint32_t n = std::min<uint32_t>(count, 0xFFFFu);  // what a 16-bit index can name
+        const auto names = [&](uint32_t e) { return data ? e != 0 : (e >> 24) != 0; };
+        std::unordered_map<uint32_t, uint64_t> value_first;
+        for (uint32_t i = 0; i < n; ++i) {
+            if (fst[i] == ~0ull || !names(old[i])) continue;
+            auto it = value_first.emplace(old[i], fst[i]).first;
+            it->second = std::min(it->second, fst[i]);
+        }
+        std::vector<std::pair<uint64_t, uint32_t>> ranked;
+        ranked.reserve(value_first.size());
+        for (const auto &kv : value_first) ranked.emplace_back(kv.second, kv.first);
+        std::sort(ranked.begin(), ranked.end());
+        std::unordered_map<uint32_t, uint32_t> index_of;
+        for (size_t r = 0; r < ranked.size(); ++r) index_of[ranked[r].second] = (uint32_t)r;
+        map.assign(0x10000, 0xFFFFu);
+        for (uint32_t i = 0; i < n; ++i) {
+            if (!names(old[i])) continue;
+            const auto it = index_of.find(old[i]);
+            if (it != index_of.end()) map[i] = it->second;
+        }
+        pal.resize(ranked.size());
+        for (size_t r = 0; r < ranked.size(); ++r) pal[r] = ranked[r].second;
+    };
     std::unique_ptr<vhx_flat> f(new vhx_flat());
+    std::vector<uint32_t> map, dmap;
+    if (do_color)
+        settle(t.color_palette, t.color_count, first, false, f->color_palette, map);
+    else
+        f->color_palette.assign(t.color_palette, t.color_palette + t.color_count);
+    if (do_data)
+        settle(t.data_palette, t.data_count, dfirst, true, f->data_palette, dmap);
+    else
+        f->data_palette.assign(t.data_palette, t.data_palette + t.data_count);
+    auto mapped = [&](uint32_t v) {
+        const uint32_t lo = do_color ? map[v & 0xFFFFu] : v & 0xFFFFu, hi = do_data ? dmap[v >> 16] : v >> 16;
+        return lo | hi << 16;
+    };
+
     f->size = t.boxtree_size;
     f->brick_dim = bd;
     f->node_type.assign(t.node_type, t.node_type + nn);
@@ -758,9 +779,6 @@ static int palette_image(const vhx_tree_desc &t, vhx_flat **out) {
     for (uint64_t i = 0; i < f->voxel_count; ++i) f->voxels[i] = mapped(t.voxels[i]);  // orphaned slots included
     f->solid_values.resize(t.solid_count);
     for (uint32_t i = 0; i < t.solid_count; ++i) f->solid_values[i] = mapped(t.solid_values[i]);
-    f->color_palette.resize(ranked.size());
-    for (size_t r = 0; r < ranked.size(); ++r) f->color_palette[r] = ranked[r].second;
-    f->data_palette.assign(t.data_palette, t.data_palette + t.data_count);
     *out = f.release();
     return VHX_OK;
 }
@@ -1158,7 +1176,17 @@ int vhx_flat_compact_palette(const vhx_tree_desc *tree, vhx_flat **out) {
     *out = nullptr;
     if (!tree) return VHX_E_INVALID_ARG;
     try {
-        return palette_image(*tree, out);
+        return palettes_image(*tree, VHX_PALETTE_COLOR, out);
+    } catch (const std::bad_alloc &) {
+        return VHX_E_CAPACITY;
+    }
+}
+int vhx_flat_compact_palettes(const vhx_tree_desc *tree, uint32_t which, vhx_flat **out) {
+    if (!out) return VHX_E_INVALID_ARG;
+    *out = nullptr;
+    if (!tree || which == 0 || (which & ~(uint32_t)(VHX_PALETTE_COLOR | VHX_PALETTE_DATA))) return VHX_E_INVALID_ARG;
+    try {
+        return palettes_image(*tree, which, out);
     } catch (const std::bad_alloc &) {
         return VHX_E_CAPACITY;
     }

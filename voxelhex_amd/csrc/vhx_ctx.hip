@@ -241,8 +241,8 @@ void vhx_destroy(vhx_ctx *c) {
                       &c->compact.bfirst, &c->compact.bnew, &c->compact.bsrc, &c->compact.ctl, &c->simplify.binfo,
                       &c->simplify.pmask, &c->simplify.gmask, &c->simplify.bfirst, &c->simplify.ent,
                       &c->simplify.bsrc, &c->simplify.newb, &c->simplify.ctl, &c->palette.org, &c->palette.first,
-                      &c->palette.map, &c->palette.ctl, &c->list.fr[0], &c->list.fr[1], &c->list.mask, &c->list.first,
-                      &c->list.unit, &c->list.ucnt, &c->list.part, &c->list.ctl, &c->list.out})
+                      &c->palette.map, &c->palette.ctl, &c->palette.dfirst, &c->palette.dmap, &c->list.fr[0],
+                      &c->list.fr[1], &c->list.mask, &c->list.first, &c->list.unit, &c->list.ucnt, &c->list.part, &c->list.ctl, &c->list.out})
         if (b->ptr) (void)hipFree(b->ptr);
     if (c->tail_stream) {
         (void)hipStreamSynchronize(c->tail_stream);

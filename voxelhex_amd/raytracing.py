@@ -619,8 +619,9 @@ class Raytracer:
         not under a streamed view; a refused call leaves the tree as it was. VHX_E_CAPACITY (tree unchanged) past 65,535
         distinct Solid values. Against read_dense + build_dense(simplify=True), the only other way back to a simplified
         tree, it needs no dense grid on the host or device, keeps data values and palette order and shrinks the buffers;
-        DESIGN.md §8.9 says how the two compare in time. The palette keeps its dead colours and its edit order, so the
-        image is the build's only up to the order of the palette; compact_palette() after it closes that caveat."""
+        DESIGN.md §8.9 says how the two compare in time. The palettes keep their dead entries and their edit order, so
+        the image is the build's only up to the order of the palettes; compact_palettes() after it closes that caveat
+        for color_palette and data_palette alike (compact_palette() for the colours alone)."""
         n, b = ctypes.c_uint32(), ctypes.c_uint32()
         self._check(N.lib().vhx_simplify_tree(self._h, ctypes.byref(n), ctypes.byref(b)))
         if not isinstance(self._tree, _BuiltOnDevice):
@@ -643,6 +644,25 @@ class Raytracer:
         if not isinstance(self._tree, _BuiltOnDevice):
             self._tree = _BuiltOnDevice()  # no longer the uploaded FlatTree: upload() of it must upload again
         return n.value
+
+    def compact_palettes(self, color=True, data=True):
+        """vhx_compact_palettes: compact_palette() for the selected halves, in one walk and one pass over the voxel
+        buffer. With data=True data_palette too becomes the builders' palette of the voxels the tree holds now: data
+        values no reachable voxel names leave, entries of one value merge, the rest is in first-appearance order of the
+        builders' insert loop, and the data half of every cell and solid value is translated (download() then equals
+        download().palettes_compacted(color, data) of before, bit for bit). After write_dense(data=), fill_box and
+        set_voxels edits, simplify() then compact_palettes() leaves exactly the image build_dense(data=, simplify=True)
+        gives for the same voxels, in all seven arrays, and compact() then compact_palettes() that of the plain build; a
+        data_palette filled up with ids no voxel holds any more (VHX_E_CAPACITY from the write calls) has room again.
+        color=True, data=False is compact_palette(). Returns (colors_dropped, data_dropped), 0 for a half that is not
+        selected. read_dense(data=True) is unchanged; contract and refusals as compact_palette(). DESIGN.md §8.14."""
+        from .boxtree import _palettes_mask
+        nc, nd = ctypes.c_uint32(), ctypes.c_uint32()
+        self._check(N.lib().vhx_compact_palettes(self._h, _palettes_mask(color, data), ctypes.byref(nc),
+                                                 ctypes.byref(nd)))
+        if not isinstance(self._tree, _BuiltOnDevice):
+            self._tree = _BuiltOnDevice()  # no longer the uploaded FlatTree: upload() of it must upload again
+        return nc.value, nd.value
 
     def update_range(self, buffer_id, elem_offset, values):
         values = np.ascontiguousarray(values)
