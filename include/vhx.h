@@ -315,6 +315,8 @@ int vhx_read_dense_data(vhx_ctx *ctx, const vhx_dense_out *box, uint32_t *data, 
  * counterpart of BoxTree::insert / clear for a tree without a host tree behind it. */
 #define VHX_WRITE_REPLACE 0u  /* every voxel of the box becomes the grid's; alpha byte 0 = no voxel (clears) */
 #define VHX_WRITE_INSERT  1u  /* grid voxels with alpha byte 0 leave the tree's voxel as it is */
+#define VHX_WRITE_UPDATE  4u  /* BoxTree::update: only the halves (colour, data value) an entry has are written, the other
+                               * half of the tree's voxel stays. 2, 3 and anything above 4 are no modes */
 typedef struct vhx_dense_in {
     uint32_t ox, oy, oz;      /* min corner of the box in the tree */
     uint32_t gx, gy, gz;      /* extents >= 1; the box must lie inside the root cube: VHX_E_INVALID_ARG otherwise */
@@ -338,7 +340,13 @@ typedef struct vhx_dense_in {
  * leaf cubes; VHX_E_INVALID_ARG for a bad box or mode. On a tree with data values the call behaves as described (cells
  * outside the box keep their data halves), and the "bit for bit a fresh build" closure with vhx_simplify_tree /
  * vhx_compact_tree holds for such a tree, in all seven buffers, with vhx_compact_palettes in place of
- * vhx_compact_palette. */
+ * vhx_compact_palette.
+ * VHX_WRITE_UPDATE is BoxTree::update over the box: a grid voxel with a colour (alpha byte not 0) recolours the tree's
+ * voxel and keeps its data value -- this is where it differs from VHX_WRITE_INSERT, which drops it -- and a grid voxel
+ * with alpha byte 0 touches nothing. An empty voxel that is recoloured becomes a Visual voxel. The new raw value is the
+ * old raw cell (the Parted brick's, the Solid value, the uniform brick's cell over the voxel; VHX_EMPTY where there was
+ * none) with its low 16 bits replaced by the colour's lowest palette index; the kept half is not tested against
+ * data_palette. Palettes, structure, numbering, ordering and refusals are those of VHX_WRITE_INSERT of the same grid. */
 int vhx_write_dense(vhx_ctx *ctx, const vhx_dense_in *box, int on_device);
 /* vhx_write_dense with user data. Every voxel of the box has an albedo word a (box->albedo, or box->fill where that is
  * NULL) and a data word d (`data`, a plane with the extents and indexing of box->albedo that lives where it lives, or
@@ -352,7 +360,14 @@ int vhx_write_dense(vhx_ctx *ctx, const vhx_dense_in *box, int on_device);
  * box's insert order), data_palette grows like the other buffers and vhx_tree_counts reports the new data_count. An
  * entry of data_palette equal to 0 is never matched. data == NULL and fill_data == 0: the call is vhx_write_dense, bit
  * for bit. Past 65,535 data values: VHX_E_CAPACITY, tree unchanged. Everything else -- Leaf nodes, Parted bricks,
- * unlinked slots, ordering, owner only, refusals -- is vhx_write_dense's contract. */
+ * unlinked slots, ordering, owner only, refusals -- is vhx_write_dense's contract.
+ * VHX_WRITE_UPDATE: the colour half of a box voxel is present when a >> 24 != 0, its data half when d != 0, and a voxel
+ * with neither touches nothing, as under VHX_WRITE_INSERT. A present half replaces that half of the tree's voxel and
+ * the other half stays (pix_overwrite_color / pix_overwrite_data on the old raw cell, VHX_EMPTY where there was none;
+ * no palette test on the kept half): a colour alone recolours and keeps the data value, a data value alone retags and
+ * keeps the colour, an empty voxel becomes Visual, Informative or Complex. vhx_read_dense_data of the cube is then
+ * what it was with the present halves replaced. New colours and data values, touched leaves and bricks, new nodes and
+ * slots, ordering and refusals are exactly those of VHX_WRITE_INSERT of the same planes. */
 int vhx_write_dense_data(vhx_ctx *ctx, const vhx_dense_in *box, const uint32_t *data, uint32_t fill_data, int on_device);
 /* A list of points written into the tree, or cleared from it, on the device and in place: the batched form of
  * BoxTree::insert(position, value) / clear(position), and the counterpart of vhx_get_voxels. The work and the scratch
@@ -363,7 +378,7 @@ typedef struct vhx_points_in {
     const uint32_t *albedo;     /* n packed colours, or NULL: every point's albedo word is `fill` */
     const uint32_t *data;       /* n data values (0 = none), or NULL: every point's data word is `fill_data` */
     uint32_t fill, fill_data;
-    uint32_t mode;              /* VHX_WRITE_REPLACE / VHX_WRITE_INSERT */
+    uint32_t mode;              /* VHX_WRITE_REPLACE / VHX_WRITE_INSERT / VHX_WRITE_UPDATE */
     uint32_t reserved0;
 } vhx_points_in;
 /* All non-null arrays live in the same place, host (copied first) or device (on_device = 1: read in place, never
@@ -390,7 +405,19 @@ typedef struct vhx_points_in {
  * the tree under an effective point is not of canonical depth; VHX_E_INVALID_ARG for a null pts, null positions with
  * n > 0, more than 2^31 points, an unknown mode, or any position outside the root cube (found on the device; ineffective
  * points count too); VHX_E_CAPACITY past 65,535 colours or data values, 2^31 bricks, 2^32 nodes or 2^28 touched leaf
- * cubes. */
+ * cubes.
+ * VHX_WRITE_UPDATE is the loop `for i in 0..n: update(positions[i], entry_i)`. The colour half of a point is present
+ * when a >> 24 != 0, its data half when d != 0; a point with neither is not effective and touches nothing (no leaf is
+ * expanded, no brick becomes Parted, no node is created). After the call the colour half of a voxel is that of the
+ * highest-index point naming it whose colour half is present, else the old one; the data half is decided the same way,
+ * independently -- a Visual and an Informative point on one voxel, in either order, leave a Complex voxel. An empty
+ * voxel that receives a half becomes Visual or Informative: update of an empty voxel is an insert. The new raw value is
+ * pix_overwrite_color / pix_overwrite_data on the old raw cell (the Parted brick's, the Solid value, the uniform
+ * brick's cell over the voxel; VHX_EMPTY where there was none): the kept 16-bit half stays as it is, with no palette
+ * test. vhx_get_voxels of a touched voxel is ci | di << 16 with the lowest indices of the new halves, and
+ * vhx_read_dense_data of the cube is what it was with the decided halves replaced. Palettes (overridden points
+ * included), touched leaves and bricks, numbering, ordering and every refusal are those of VHX_WRITE_INSERT on the same
+ * effective set. */
 int vhx_set_voxels(vhx_ctx *ctx, const vhx_points_in *pts, int on_device);
 /* The occupied voxels of a box of the tree as a list: the sparse form of vhx_read_dense_data and the inverse of
  * vhx_set_voxels. The work and the scratch follow the nodes and bricks under the box, not its volume. */

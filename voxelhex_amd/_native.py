@@ -47,6 +47,7 @@ VHX_BUF_NODE_TYPE, VHX_BUF_NODE_OCBITS, VHX_BUF_NODE_CHILDREN, VHX_BUF_VOXELS = 
 VHX_BUF_SOLID_VALUES, VHX_BUF_COLOR_PALETTE, VHX_BUF_DATA_PALETTE = 4, 5, 6
 VHX_DERIVED_NODE_HDR, VHX_DERIVED_BRICK_OCC = 0, 1
 VHX_WRITE_REPLACE, VHX_WRITE_INSERT = 0, 1
+VHX_WRITE_UPDATE = 4  # 2 and 3 are no modes
 VHX_PALETTE_COLOR, VHX_PALETTE_DATA = 1, 2
 
 

@@ -119,7 +119,9 @@ __global__ __launch_bounds__(256) void k_edit_walk(EditP p, TreeP t, Scratch s, 
 // ballots run with all 64 lanes.
 // DATA = 1 (vhx_write_dense_data): a box voxel is an entry where it has a colour or a data value, its data values go
 // into `dtab`, and the emission writes both halves.
-template <int EMIT, int DATA>
+// UPD = 1 (VHX_WRITE_UPDATE): a box voxel with an entry is covered, and its value is the old raw cell
+// with the halves the entry has replaced (pix_overwrite_color / pix_overwrite_data); without DATA the data half stays.
+template <int EMIT, int DATA, int UPD>
 __global__ __launch_bounds__(256) void k_edit_leaf(EditP p, TreeP t, Scratch s, ColorTable tab, ColorTable dtab,
                                                    EditCtl *ctl) {
     __shared__ uint32_t s_ty, s_u, s_orph;
@@ -129,6 +131,7 @@ __global__ __launch_bounds__(256) void k_edit_leaf(EditP p, TreeP t, Scratch s, 
     const uint64_t nleaf = (uint64_t)L.n[0] * L.n[1] * L.n[2];
     const uint32_t bd = 1u << p.lg_bd, n3 = 1u << (3u * p.lg_bd), lsh = p.lg_bd + 2u;
     uint32_t last_c = 0, last_d = 0, last_v = VHX_EMPTY;
+    uint32_t last_ci = 0xFFFFu, last_di = 0xFFFFu;  // UPD: the two looked-up indices; the spliced value is per cell
     for (uint64_t cell = blockIdx.x; cell < nleaf; cell += gridDim.x) {
         const uint32_t node = s.oldn[L.off + cell];
         const u64 aft = EMIT ? s.aft[L.off + cell] : 0ull;
@@ -199,7 +202,7 @@ __global__ __launch_bounds__(256) void k_edit_leaf(EditP p, TreeP t, Scratch s, 
                 if (DATA && inbox) gd = p.dgrid ? p.dgrid[((uint64_t)rz * p.gy + ry) * p.gx + rx] : p.dfill;
                 const bool col = (g >> 24) != 0;  // the voxel has a colour
                 const bool vis = col || (DATA && gd != 0);  // the box's voxel is an entry
-                const bool covered = inbox && (p.mode == VHX_WRITE_REPLACE || vis);
+                const bool covered = inbox && ((!UPD && p.mode == VHX_WRITE_REPLACE) || vis);
                 uint32_t raw = VHX_EMPTY;
                 bool ne = false;
                 if (own) {
@@ -235,7 +238,26 @@ __global__ __launch_bounds__(256) void k_edit_leaf(EditP p, TreeP t, Scratch s, 
                     }
                 } else {
                     const uint64_t va = ((uint64_t)slot << (3u * p.lg_bd)) + c;
-                    if (covered) {
+                    if (UPD && covered) {
+                        // the old raw cell (VHX_EMPTY where there was none); an own brick's is read only where a half
+                        // of it is kept
+                        uint32_t v = own ? ((col && gd) ? 0u : t.voxels[va]) : raw;
+                        if (col) {
+                            if (g != last_c) {
+                                last_c = g;
+                                last_ci = color_lookup(tab, g);
+                            }
+                            v = (v & 0xFFFF0000u) | last_ci;
+                        }
+                        if (DATA && gd) {
+                            if (gd != last_d) {
+                                last_d = gd;
+                                last_di = color_lookup(dtab, gd);
+                            }
+                            v = (v & 0x0000FFFFu) | (last_di << 16);
+                        }
+                        t.voxels[va] = v;
+                    } else if (covered) {
                         uint32_t v = VHX_EMPTY;
                         if (vis) {
                             const uint32_t gc = col ? g : 0u;
@@ -359,7 +381,7 @@ int write_dense(vhx_ctx *c, const vhx_dense_in *box, const uint32_t *data, uint3
     if (box->gx == 0 || box->gy == 0 || box->gz == 0 || (uint64_t)box->ox + box->gx > S ||
         (uint64_t)box->oy + box->gy > S || (uint64_t)box->oz + box->gz > S)
         return fail(c, VHX_E_INVALID_ARG, "vhx_write_dense: an extent of 0, or a box outside the root cube");
-    if (box->mode != VHX_WRITE_REPLACE && box->mode != VHX_WRITE_INSERT)
+    if (box->mode != VHX_WRITE_REPLACE && box->mode != VHX_WRITE_INSERT && box->mode != VHX_WRITE_UPDATE)
         return fail(c, VHX_E_INVALID_ARG, "vhx_write_dense: unknown mode");
     EditP p{};
     p.ox = box->ox, p.oy = box->oy, p.oz = box->oz;
@@ -443,10 +465,15 @@ int write_dense(vhx_ctx *c, const vhx_dense_in *box, const uint32_t *data, uint3
     if (with_data)
         k_edit_seed<1><<<blocks_for((uint64_t)d.data_count + 1), 256, 0, c->stream>>>(dtab, t.data, d.data_count, ctl);
     const unsigned leaf_blocks = (unsigned)std::min<uint64_t>(nleaf, (uint64_t)c->cus * 32);
-    if (with_data)
-        k_edit_leaf<0, 1><<<leaf_blocks, 256, 0, c->stream>>>(p, t, s, tab, dtab, ctl);
+    const bool upd = p.mode == VHX_WRITE_UPDATE;
+    if (upd && with_data)
+        k_edit_leaf<0, 1, 1><<<leaf_blocks, 256, 0, c->stream>>>(p, t, s, tab, dtab, ctl);
+    else if (upd)
+        k_edit_leaf<0, 0, 1><<<leaf_blocks, 256, 0, c->stream>>>(p, t, s, tab, dtab, ctl);
+    else if (with_data)
+        k_edit_leaf<0, 1, 0><<<leaf_blocks, 256, 0, c->stream>>>(p, t, s, tab, dtab, ctl);
     else
-        k_edit_leaf<0, 0><<<leaf_blocks, 256, 0, c->stream>>>(p, t, s, tab, dtab, ctl);
+        k_edit_leaf<0, 0, 0><<<leaf_blocks, 256, 0, c->stream>>>(p, t, s, tab, dtab, ctl);
     for (uint32_t lv = p.D; lv-- > 0;) {
         const Lattice &L = p.lv[lv];
         k_edit_reduce<<<blocks_for((uint64_t)L.n[0] * L.n[1] * L.n[2]), 256, 0, c->stream>>>(p, t, s, lv, ctl);
@@ -496,10 +523,14 @@ int write_dense(vhx_ctx *c, const vhx_dense_in *box, const uint32_t *data, uint3
     if ((rc = vhx::grow_tree(c, &nd))) return rc;
     t = tree_of(c, d);  // the buffers may have moved; the counts stay the old ones
 
-    if (with_data)
-        k_edit_leaf<1, 1><<<leaf_blocks, 256, 0, c->stream>>>(p, t, s, tab, dtab, ctl);
+    if (upd && with_data)
+        k_edit_leaf<1, 1, 1><<<leaf_blocks, 256, 0, c->stream>>>(p, t, s, tab, dtab, ctl);
+    else if (upd)
+        k_edit_leaf<1, 0, 1><<<leaf_blocks, 256, 0, c->stream>>>(p, t, s, tab, dtab, ctl);
+    else if (with_data)
+        k_edit_leaf<1, 1, 0><<<leaf_blocks, 256, 0, c->stream>>>(p, t, s, tab, dtab, ctl);
     else
-        k_edit_leaf<1, 0><<<leaf_blocks, 256, 0, c->stream>>>(p, t, s, tab, dtab, ctl);
+        k_edit_leaf<1, 0, 0><<<leaf_blocks, 256, 0, c->stream>>>(p, t, s, tab, dtab, ctl);
     for (uint32_t lv = 0; lv <= p.D; ++lv) {
         const Lattice &L = p.lv[lv];
         k_edit_nodes<<<blocks_for((uint64_t)L.n[0] * L.n[1] * L.n[2] * 64), 256, 0, c->stream>>>(p, t, s, lv);

@@ -2,7 +2,8 @@
 //
 // vhx_write_dense (vhx_edit.hip) with sparse per-level lists of touched cubes in place of the box's lattices: the work
 // and the scratch follow the points and the bricks they touch, not their bounding box. A point is effective when its
-// mode lets it decide its voxel (replace: every point; insert: a point with a colour or a data value). The passes:
+// mode lets it decide its voxel (replace: every point; insert and update: a point with a colour or a data value). The
+// passes:
 //
 //   first    k_pts_first     bounds, the points' colours and data values into the tables (first index NEW_BASE + i), the
 //                            root's sectants that hold an effective point
@@ -15,7 +16,9 @@
 //   group    k_pts_count, k_scan_*, k_pts_scatter   point indices in per-brick segments (any order inside a segment)
 //   bricks   k_pts_brick<0>  a wave per touched brick: the highest point index per cell by atomicMax in LDS (chunks of
 //                            1024 cells), the old bitmap, Solid value or uniform cell for the undecided cells, the
-//                            brick's bitmap after the write by ballot; "exists", "needs a new slot", "orphaned"
+//                            brick's bitmap after the write by ballot; "exists", "needs a new slot", "orphaned".
+//                            VHX_WRITE_UPDATE (UPD = 1) keeps two maxima per cell, the highest point
+//                            with a colour half and the highest with a data half, and splices them into the old cell
 //   levels   k_pts_leaf, k_pts_reduce   occupancy after the write, upwards; "must exist and does not" per cube
 //   scans, palette  as vhx_write_dense
 //   -- the last readback of counters; nothing of the tree has been written so far; then the buffers grow --
@@ -244,16 +247,35 @@ __global__ __launch_bounds__(256) void k_pts_scatter(PtsP p, PtsS s) {
     s.idx[s.bseg[b] + left - 1ull] = (uint32_t)gid;
 }
 
+// The wave's winners in LDS. REPLACE and INSERT keep their static 4 x 1024 words; UPDATE has two arrays per wave (colour
+// winners, then data winners), sized to the chunk at launch: 2 KiB per workgroup at brick_dim 4, 32 KiB from brick_dim 16.
+template <int UPD>
+__device__ __forceinline__ uint32_t *win_lds(uint32_t wave, uint32_t ch);
+template <>
+__device__ __forceinline__ uint32_t *win_lds<0>(uint32_t wave, uint32_t) {
+    __shared__ uint32_t s_win[4][CHUNK];
+    return s_win[wave];
+}
+template <>
+__device__ __forceinline__ uint32_t *win_lds<1>(uint32_t wave, uint32_t ch) {
+    extern __shared__ uint32_t s_dyn[];
+    return s_dyn + wave * ch;
+}
+
 // The touched bricks, a wave each. EMIT = 0 analyses (reads the tree only), EMIT = 1 writes; both derive the brick's
 // bitmap after the write the same way. Loop bounds are wave uniform: the ballots run with all 64 lanes.
-template <int EMIT>
+// UPD = 1 (VHX_WRITE_UPDATE): a cell has two winners, the highest point with a colour half and the highest with a data
+// half (a second array of the chunk's size); a decided cell is the old raw cell with the decided halves replaced, and
+// is never empty.
+template <int EMIT, int UPD>
 __global__ __launch_bounds__(256) void k_pts_brick(PtsP p, TreeP t, PtsS s, ColorTable tab, ColorTable dtab, PtsCtl *ctl,
                                                    uint64_t nb) {
-    __shared__ uint32_t s_win[4][CHUNK];  // per cell of the chunk: the highest index of a point there, plus 1; 0 = none
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint64_t b = (uint64_t)blockIdx.x * 4u + wave;
     if (b >= nb) return;  // the whole wave; the kernel has no workgroup barrier
-    uint32_t *win = s_win[wave];
+    // per cell of the chunk: the highest index of a point there, plus 1; 0 = none
+    uint32_t *win = win_lds<UPD>(wave, min(1u << (3u * p.lg_bd), CHUNK));
+    uint32_t *wind = win + (UPD ? 4u * min(1u << (3u * p.lg_bd), CHUNK) : 0u);  // UPD: the data halves' winners
     const uint64_t info = s.binfo[b];
     const uint64_t L = info >> 6, LL = p.off[p.D] + L;
     const uint32_t sec = (uint32_t)info & 63u;
@@ -285,22 +307,40 @@ __global__ __launch_bounds__(256) void k_pts_brick(PtsP p, TreeP t, PtsS s, Colo
     const uint64_t j0 = s.bseg[b], j1 = b + 1 < nb ? s.bseg[b + 1] : ctl->count[p.D + 2];
     u64 any = 0, word0 = 0;
     for (uint32_t c0 = 0; c0 < n3; c0 += ch) {
-        for (uint32_t k = lane; k < ch; k += 64u) win[k] = 0u;
+        for (uint32_t k = lane; k < ch; k += 64u) {
+            win[k] = 0u;
+            if (UPD) wind[k] = 0u;
+        }
         __threadfence_block();  // the wave's LDS operations run in order; this keeps the compiler from moving them
         for (uint64_t j = j0 + lane; j < j1; j += 64u) {
             const uint32_t i = s.idx[j];
             const uint32_t x = p.pos[3ull * i], y = p.pos[3ull * i + 1], z = p.pos[3ull * i + 2];
             const uint32_t c = (x & (bd - 1u)) | ((y & (bd - 1u)) << p.lg_bd) | ((z & (bd - 1u)) << (2u * p.lg_bd));
-            if (c - c0 < ch) atomicMax(&win[c - c0], i + 1u);
+            if (c - c0 < ch) {
+                if (UPD) {  // every point of a segment is effective: it has one half at least
+                    uint32_t pa, pd;
+                    point_words(p, i, pa, pd);
+                    if ((pa >> 24) != 0) atomicMax(&win[c - c0], i + 1u);
+                    if (pd != 0) atomicMax(&wind[c - c0], i + 1u);
+                } else {
+                    atomicMax(&win[c - c0], i + 1u);
+                }
+            }
         }
         __threadfence_block();
         for (uint32_t k0 = 0; k0 < ch; k0 += 64u) {
             const uint32_t k = k0 + lane, c = c0 + k;
             const bool valid = k < ch;
             const uint32_t w = valid ? win[k] : 0u;
-            const bool decided = w != 0u;
+            const uint32_t wd = UPD && valid ? wind[k] : 0u;
+            const bool decided = (w | wd) != 0u;
             uint32_t a = 0, dv = 0;
-            if (decided) point_words(p, w - 1u, a, dv);
+            if (UPD) {  // each half from its own winner
+                if (w) a = p.albedo ? p.albedo[w - 1u] : p.fill;
+                if (wd) dv = p.data ? p.data[wd - 1u] : p.dfill;
+            } else if (decided) {
+                point_words(p, w - 1u, a, dv);
+            }
             const bool col = (a >> 24) != 0;
             const bool vis = col || dv != 0;  // the deciding point writes an entry; else it clears (replace mode)
             uint32_t raw = VHX_EMPTY;
@@ -325,7 +365,14 @@ __global__ __launch_bounds__(256) void k_pts_brick(PtsP p, TreeP t, PtsS s, Colo
             if (c0 + k0 == 0) word0 = word;
             if (EMIT) {
                 const uint64_t va = ((uint64_t)slot << (3u * p.lg_bd)) + c;
-                if (decided) {
+                if (UPD && decided) {
+                    // pix_overwrite_color / pix_overwrite_data on the old raw cell (VHX_EMPTY where there was none); an
+                    // own brick's cell is read here, and only where a half of it is kept
+                    uint32_t v = own ? ((col && dv) ? 0u : t.voxels[va]) : raw;
+                    if (col) v = (v & 0xFFFF0000u) | color_lookup(tab, a);
+                    if (dv) v = (v & 0x0000FFFFu) | (color_lookup(dtab, dv) << 16);
+                    t.voxels[va] = v;
+                } else if (decided) {
                     uint32_t v = VHX_EMPTY;
                     // pix_visual, pix_informative, pix_complex: 0xFFFF for the half that is none
                     if (vis) v = (col ? color_lookup(tab, a) : 0xFFFFu) | ((dv ? color_lookup(dtab, dv) : 0xFFFFu) << 16);
@@ -451,7 +498,7 @@ int set_voxels(vhx_ctx *c, const vhx_points_in *pts, int on_device) {
     if (!c || !pts) return fail(c, VHX_E_INVALID_ARG, "vhx_set_voxels: null argument");
     if (pts->n > 0 && !pts->positions) return fail(c, VHX_E_INVALID_ARG, "vhx_set_voxels: null positions");
     if (pts->n > (1ull << 31)) return fail(c, VHX_E_INVALID_ARG, "vhx_set_voxels: more than 2^31 points");
-    if (pts->mode != VHX_WRITE_REPLACE && pts->mode != VHX_WRITE_INSERT)
+    if (pts->mode != VHX_WRITE_REPLACE && pts->mode != VHX_WRITE_INSERT && pts->mode != VHX_WRITE_UPDATE)
         return fail(c, VHX_E_INVALID_ARG, "vhx_set_voxels: unknown mode");
     if (c->shared) return fail(c, VHX_E_STATE, "vhx_set_voxels on a shared context: write through the owner");
     if (!c->tree->uploaded) return fail(c, VHX_E_STATE, "vhx_set_voxels before vhx_upload_tree");
@@ -569,7 +616,7 @@ int set_voxels(vhx_ctx *c, const vhx_points_in *pts, int on_device) {
     if (h.e.bad)
         return fail(c, VHX_E_STATE, "vhx_set_voxels: the tree under a point is not of canonical depth (a LOD-cut or "
                                     "streamed view)");
-    if (!h.neff) return ws.end();  // insert mode, and no point has an entry
+    if (!h.neff) return ws.end();  // insert or update mode, and no point has an entry
     const uint64_t nleaf = h.count[p.D], nb = h.count[p.D + 1];
     if (nleaf > MAX_LEAVES) return fail(c, VHX_E_CAPACITY, "vhx_set_voxels: more than 2^28 touched leaf cubes");
     if (nb >= 0x80000000ull) return fail(c, VHX_E_CAPACITY, "vhx_set_voxels: 2^31 touched bricks or more");
@@ -587,7 +634,12 @@ int set_voxels(vhx_ctx *c, const vhx_points_in *pts, int on_device) {
     if ((rc = scan_level<3>(c, s.bcnt, nb, false, s.bseg, &ctl->count[p.D + 2]))) return rc;
     k_pts_scatter<<<blocks_for(p.n), 256, 0, c->stream>>>(p, s);
     const unsigned brick_blocks = (unsigned)((nb + 3) / 4);
-    k_pts_brick<0><<<brick_blocks, 256, 0, c->stream>>>(p, t, s, tab, dtab, ctl, nb);
+    const bool upd = p.mode == VHX_WRITE_UPDATE;
+    const size_t upd_lds = 8u * std::min<size_t>((size_t)1 << (3u * p.lg_bd), CHUNK) * sizeof(uint32_t);
+    if (upd)
+        k_pts_brick<0, 1><<<brick_blocks, 256, upd_lds, c->stream>>>(p, t, s, tab, dtab, ctl, nb);
+    else
+        k_pts_brick<0, 0><<<brick_blocks, 256, 0, c->stream>>>(p, t, s, tab, dtab, ctl, nb);
     k_pts_leaf<<<blocks_for(nleaf), 256, 0, c->stream>>>(p, t, s, ctl, nleaf);
     for (uint32_t lv = p.D; lv-- > 0;)
         k_pts_reduce<<<blocks_for(h.count[lv]), 256, 0, c->stream>>>(p, t, s, ctl, lv, h.count[lv]);
@@ -629,7 +681,10 @@ int set_voxels(vhx_ctx *c, const vhx_points_in *pts, int on_device) {
     if ((rc = vhx::grow_tree(c, &nd))) return rc;
     t = tree_of(c, d);  // the buffers may have moved; the counts stay the old ones
 
-    k_pts_brick<1><<<brick_blocks, 256, 0, c->stream>>>(p, t, s, tab, dtab, ctl, nb);
+    if (upd)
+        k_pts_brick<1, 1><<<brick_blocks, 256, upd_lds, c->stream>>>(p, t, s, tab, dtab, ctl, nb);
+    else
+        k_pts_brick<1, 0><<<brick_blocks, 256, 0, c->stream>>>(p, t, s, tab, dtab, ctl, nb);
     for (uint32_t lv = 0; lv <= p.D; ++lv)
         k_pts_nodes<<<blocks_for(h.count[lv] * 64u), 256, 0, c->stream>>>(p, t, s, lv, h.count[lv]);
     VHX_HIP(c, hipGetLastError());

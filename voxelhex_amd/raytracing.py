@@ -429,8 +429,12 @@ class Raytracer:
         shape and device as `grid`, or an integer that every voxel of the box gets. A voxel of the box is then an entry
         where it has a colour or a data value ("replace" clears where it has neither, "insert" leaves the tree alone
         there), and a written voxel is replaced wholesale: an old data value does not survive under a colour written
-        without one. New data values follow the data palette in the box's insert order."""
-        modes = {"replace": N.VHX_WRITE_REPLACE, "insert": N.VHX_WRITE_INSERT}
+        without one. New data values follow the data palette in the box's insert order.
+        mode "update" (VHX_WRITE_UPDATE, the batched BoxTree.update) merges instead: a grid voxel with a colour
+        recolours the tree's voxel and keeps its data value, a `data` value other than 0 retags it and keeps its colour,
+        a voxel of the box with neither touches nothing, and an empty voxel that receives a half becomes a voxel.
+        Without `data` the data values under the box stay as they are."""
+        modes = {"replace": N.VHX_WRITE_REPLACE, "insert": N.VHX_WRITE_INSERT, "update": N.VHX_WRITE_UPDATE}
         box = N.DenseIn()
         box.ox, box.oy, box.oz = (int(v) for v in origin)
         box.mode = modes[mode] if mode in modes else int(mode)
@@ -454,16 +458,20 @@ class Raytracer:
             self._check(N.lib().vhx_write_dense_data(self._h, ctypes.byref(box), ptr, 0, on_device))
             del keep
 
-    def fill_box(self, origin, extents, albedo, data=0):
+    def fill_box(self, origin, extents, albedo, data=0, mode="replace"):
         """vhx_write_dense without a grid: every voxel of the box at `origin` with `extents` (gx, gy, gz) becomes the
         packed colour `albedo`; 0 (or any colour with alpha 0) clears the box. `data` (vhx_write_dense_data) is the
         user data value every voxel of the box gets beside the colour, 0 = none -- fill_box(o, e, 0, 7) writes
         data-only voxels, fill_box(o, e, 0, 0) clears -- or a plane of shape (gz, gy, gx) with a value per voxel (a
-        uint32 numpy array or a device tensor)."""
+        uint32 numpy array or a device tensor). `mode` is write_dense's: under "update" only the halves given are
+        written -- fill_box(o, e, 0, 7, mode="update") gives every voxel of the box the data value 7, occupied ones
+        keep their colour and empty ones become data-only voxels; fill_box(o, e, colour, 0, mode="update") recolours
+        the box and keeps its data values."""
+        modes = {"replace": N.VHX_WRITE_REPLACE, "insert": N.VHX_WRITE_INSERT, "update": N.VHX_WRITE_UPDATE}
         box = N.DenseIn()
         box.ox, box.oy, box.oz = (int(v) for v in origin)
         box.gx, box.gy, box.gz = (int(v) for v in extents)
-        box.mode, box.fill, box.albedo = N.VHX_WRITE_REPLACE, int(albedo), None
+        box.mode, box.fill, box.albedo = modes[mode] if mode in modes else int(mode), int(albedo), None
         if isinstance(data, (int, np.integer)):
             if int(data) == 0:
                 self._check(N.lib().vhx_write_dense(self._h, ctypes.byref(box), 0))
@@ -491,8 +499,12 @@ class Raytracer:
         clears its voxel under mode "replace" and touches nothing under "insert". The result is that of the loop over
         the list: where points repeat a position the last one decides. New colours and data values follow the palettes
         in list order. Owner context only; the call returns when the tree is ready; slots are never reused (orphans(),
-        compact()). Cost and scratch follow the points and the bricks they touch, not their bounding box."""
-        modes = {"replace": N.VHX_WRITE_REPLACE, "insert": N.VHX_WRITE_INSERT}
+        compact()). Cost and scratch follow the points and the bricks they touch, not their bounding box.
+        mode "update" (VHX_WRITE_UPDATE, the batched BoxTree.update) merges halves instead of replacing voxels: a
+        point's colour (alpha not 0) replaces the voxel's colour, its data value (not 0) the voxel's data value, and
+        the half a point does not have stays what it was; a point with neither touches nothing. Where points repeat a
+        position, the last one with a colour decides the colour and the last one with a data value the data value."""
+        modes = {"replace": N.VHX_WRITE_REPLACE, "insert": N.VHX_WRITE_INSERT, "update": N.VHX_WRITE_UPDATE}
         pts = N.PointsIn()
         pts.mode = modes[mode] if mode in modes else int(mode)
         keep = []
@@ -531,6 +543,12 @@ class Raytracer:
             keep.append(w)
         self._check(N.lib().vhx_set_voxels(self._h, ctypes.byref(pts), on_device))
         del keep
+
+    def update_voxels(self, positions, albedo=None, data=None):
+        """set_voxels(..., "update"): the listed voxels recoloured (`albedo`) and / or retagged (`data`), the half that
+        is not given -- None, 0, or a 0 in an array -- kept as it is. update_voxels(pos, data=7) gives the voxels the
+        data value 7 and keeps their colours; an empty voxel among them becomes a data-only voxel."""
+        self.set_voxels(positions, albedo, data, "update")
 
     def clear_voxels(self, positions):
         """vhx_set_voxels without values: every listed voxel is cleared (the batched BoxTree.clear)."""
