@@ -625,6 +625,40 @@ int vhx_set_shadow_light(vhx_ctx *ctx, const float *light);
  * it goes through the owner of a shared tree and is ordered against frames in flight (vhx_create_shared); shared
  * contexts trace with them. */
 int vhx_set_node_mips(vhx_ctx *ctx, const uint32_t *node_mips, uint32_t count);
+/* The node MIP descriptors in force (vhx_set_node_mips, vhx_build_lod): out[0 .. count) receives them, count must equal
+ * the tree's node_count. A trace-like read, allowed on shared contexts. VHX_E_STATE when none are set. */
+int vhx_read_node_mips(vhx_ctx *ctx, uint32_t *out, uint32_t count);
+/* Gives `dst` the LOD image of the resident tree of `src` with node MIPs, computed on the device: the image of
+ * vhx_flat_lod (vhx_boxtree.h) of src's tree, bit for bit in all seven buffers and in the descriptors, which are set on
+ * dst as vhx_set_node_mips sets them. src is only read: it stays MIP-free and editable, and a renderer calls this again
+ * after edits. `method` is VHX_MIP_BOX_FILTER (0) or VHX_MIP_POINT_FILTER (1) of vhx_boxtree.h, applied on every level
+ * with every colour-similarity threshold at 0. The rules, which are BoxTree::recalculate_mips' and the flattener's:
+ *   Every Leaf and Internal node reachable from node 0 gets a MIP brick of brick_dim^3 cells; a UniformLeaf or Nothing
+ *     node has none. A cell samples the 4x4x4 block under it, x outer, y, z inner: of a Leaf the voxels (a Solid brick
+ *     gives its value, a Parted cell its word unless it points to empty, an empty entry nothing), of an Internal node
+ *     the cells of its children's MIP bricks (an absent child or one without a MIP gives nothing). Only a sample's
+ *     colour counts: the palette entry of its colour index, where that index is not 0xFFFF and below color_count.
+ *   BoxFilter: per channel sqrt(sum(c^2) / n) in f32, min(., 255), truncated. PointFilter: the most frequent colour, a
+ *     tie going to the tied colour first met latest in the scan.
+ *   A cell that sampled nothing, or whose colour is the word 0, is VHX_EMPTY; any other is its colour's palette index
+ *     | 0xFFFF0000. A node with one sampled cell has a Parted MIP brick, any other node the descriptor VHX_EMPTY.
+ *   A colour the palette does not hold is appended. New colours are ordered by first use in the serial order: nodes in
+ *     post-order (children in sectant order before their parent), cells x outer, y, z inner. This happens for the whole
+ *     tree, before the cut. A palette that holds a colour twice gives an unspecified index for it.
+ *   Nodes deeper than max_depth (root = 0) are left out; their parents' entries become VHX_EMPTY, occupied_bits stay.
+ *     Nodes are numbered breadth-first as vhx_compact_tree numbers them, bricks in that node order: a node's Parted
+ *     bricks in sectant order, then its MIP brick. solid_values are the distinct values of the kept Solid entries by
+ *     first (node, sectant). data_palette is src's. A max_depth at or past the tree's depth keeps every node.
+ * *nodes, *bricks and *colors_added receive the image's node and brick counts and the colours appended.
+ * Ordering and refusals on dst are vhx_build_tree_dense's: owner context only (VHX_E_STATE on a shared one), frames
+ * submitted before the call see dst's old tree, frames after it the new one with its MIPs, the call returns when the
+ * tree is ready, and a refused call leaves both contexts bit for bit as they were. On src the call is a trace-like read.
+ * VHX_E_INVALID_ARG: a null argument, an unknown method, dst and src on one tree or on different devices. VHX_E_STATE:
+ * src without a tree, with node MIPs set, malformed (vhx_compact_tree's cases) or not of canonical depth (a LOD-cut
+ * or streamed view, a Leaf or UniformLeaf whose edge is not 4 * brick_dim); dst with a shadow light set. VHX_E_CAPACITY:
+ * more than 65,535 colours, or 2^31 bricks or more. */
+int vhx_build_lod(vhx_ctx *dst, vhx_ctx *src, uint32_t max_depth, uint32_t method, uint32_t *nodes, uint32_t *bricks,
+                  uint32_t *colors_added);
 /* Diagnostics of a VHX_PROF build (scripts/probes/probe_blocks.py; a regular build returns VHX_E_STATE): per pass
  * slot (5: budgets <= 24, <= 96, <= 256, larger, the unbounded pass) and traversal block (16), the wave executions
  * and the lanes active in them, as out[2 * (pass * 16 + block)] and out[2 * (pass * 16 + block) + 1], accumulated

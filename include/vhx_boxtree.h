@@ -266,6 +266,14 @@ int vhx_flat_compact_palettes(const vhx_tree_desc *tree, uint32_t which, vhx_fla
  * Refusals as the device call, with VHX_E_INVALID_ARG also for a null tree, null node arrays, a count of 0 nodes and a
  * size that is not brick_dim * 4^k. */
 int vhx_flat_list_voxels(const vhx_tree_desc *tree, const vhx_points_out *q);
+/* The LOD image of `tree` with node MIPs: vhx_flat_compact, the host BoxTree of that image, `method`
+ * (VHX_MIP_BOX_FILTER or VHX_MIP_POINT_FILTER) with a colour-similarity threshold of 0 set on every MIP level,
+ * vhx_boxtree_switch_mips(1) and vhx_boxtree_flatten_lod(max_depth) in one call (no algorithm of its own); the CPU
+ * counterpart of vhx_build_lod (vhx.h, which states the rules), bit for bit in all seven buffers and in the node MIPs
+ * (vhx_flat_node_mips). The MIPs are computed for the whole tree before the cut, so the colours of the nodes that are
+ * left out are in color_palette as well. Errors as vhx_flat_simplify (a palette with duplicate or empty entries is
+ * refused); VHX_E_INVALID_ARG for any other method; VHX_E_CAPACITY where the palette would pass 65,535 colours. */
+int vhx_flat_lod(const vhx_tree_desc *tree, uint32_t max_depth, uint32_t method, vhx_flat **out);
 void vhx_flat_free(vhx_flat *flat);
 
 /* MagicaVoxel .vox import — BoxTree::<u32>::load_vox_file(filename, brick_dimension) (src/convert/magicavoxel.rs:

@@ -27,7 +27,8 @@ HOST_SRCS = ["boxtree.cpp", "flatten.cpp", "vox.cpp", "stream.cpp"]
 # with the default scheduler; trace kernels 70 / 97 VGPRs against 75 / 102 (profiles/r02/sched_variants_f8.log)
 DEV_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
 DEV_SRCS = ["vhx_device.hip", "vhx_tree.hip", "vhx_ctx.hip", "vhx_mgpu.hip", "vhx_build.hip", "vhx_query.hip",
-            "vhx_edit.hip", "vhx_points.hip", "vhx_compact.hip", "vhx_simplify.hip", "vhx_palette.hip", "vhx_list.hip"]
+            "vhx_edit.hip", "vhx_points.hip", "vhx_compact.hip", "vhx_simplify.hip", "vhx_palette.hip", "vhx_list.hip",
+            "vhx_lod.hip"]
 HEADERS = ["boxtree.hpp", "trace.hpp", "ctx.hpp", "skyblock.hpp", "buildtab.hpp", "edittab.hpp", "treewalk.hpp",
            "treepack.hpp"]
 

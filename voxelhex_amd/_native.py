@@ -49,6 +49,7 @@ VHX_DERIVED_NODE_HDR, VHX_DERIVED_BRICK_OCC = 0, 1
 VHX_WRITE_REPLACE, VHX_WRITE_INSERT = 0, 1
 VHX_WRITE_UPDATE = 4  # 2 and 3 are no modes
 VHX_PALETTE_COLOR, VHX_PALETTE_DATA = 1, 2
+VHX_MIP_BOX_FILTER, VHX_MIP_POINT_FILTER = 0, 1
 
 
 class TreeDesc(ctypes.Structure):
@@ -154,6 +155,8 @@ SIGNATURES = [
     ("vhx_compact_palette", c_int, [c_void_p, P(c_u32)]),
     ("vhx_compact_palettes", c_int, [c_void_p, c_u32, P(c_u32), P(c_u32)]),
     ("vhx_set_node_mips", c_int, [c_void_p, c_void_p, c_u32]),
+    ("vhx_read_node_mips", c_int, [c_void_p, c_void_p, c_u32]),
+    ("vhx_build_lod", c_int, [c_void_p, c_void_p, c_u32, c_u32, P(c_u32), P(c_u32), P(c_u32)]),
     ("vhx_update_range", c_int, [c_void_p, c_int, c_u64, c_u64, c_void_p]),
     ("vhx_update_ranges", c_int, [c_void_p, c_void_p, c_u32]),
     ("vhx_set_depth_prepass", c_int, [c_void_p, c_int, ctypes.c_float]),
@@ -233,6 +236,7 @@ SIGNATURES = [
     ("vhx_flat_compact_palette", c_int, [P(TreeDesc), P(c_void_p)]),
     ("vhx_flat_compact_palettes", c_int, [P(TreeDesc), c_u32, P(c_void_p)]),
     ("vhx_flat_list_voxels", c_int, [P(TreeDesc), P(PointsOut)]),
+    ("vhx_flat_lod", c_int, [P(TreeDesc), c_u32, c_u32, P(c_void_p)]),
     ("vhx_boxtree_switch_mips", c_int, [c_void_p, c_int]),
     ("vhx_boxtree_set_mip_method", c_int, [c_void_p, c_u32, c_u32, c_f32]),
     ("vhx_boxtree_set_mip_color_threshold", c_int, [c_void_p, c_u32, c_f32]),

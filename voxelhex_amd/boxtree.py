@@ -326,6 +326,33 @@ def _palettes_compacted(image, color, data):
     return FlatTree(h.value)
 
 
+def mip_method_code(method):
+    """VHX_MIP_BOX_FILTER / VHX_MIP_POINT_FILTER of "box" / "point", a MIPResamplingMethods pair or the code itself."""
+    if isinstance(method, str):
+        try:
+            return {"box": N.VHX_MIP_BOX_FILTER, "point": N.VHX_MIP_POINT_FILTER}[method]
+        except KeyError:
+            raise ValueError(f"lod: the method is 'box' or 'point', not {method!r}") from None
+    return int(method[0] if isinstance(method, tuple) else method)
+
+
+def _lod(image, max_depth, method):
+    """vhx_flat_lod of a FlatTree or TreeImage, as a new FlatTree with its node_mips."""
+    h = ctypes.c_void_p()
+    _tree_check(N.lib().vhx_flat_lod(ctypes.byref(image.desc), int(max_depth), mip_method_code(method),
+                                     ctypes.byref(h)), "lod: a malformed image, or more than 65,535 colours")
+    return FlatTree(h.value)
+
+
+_LOD_DOC = """vhx_flat_lod: the LOD image of this image with node MIPs, as a FlatTree whose node_mips holds the
+        descriptors -- what Raytracer.build_lod(source, max_depth, method) gives the destination on the device, bit for
+        bit. `method` is "box" (BoxFilter) or "point" (PointFilter), applied on every level with every colour-similarity
+        threshold at 0; the MIPs are those BoxTree's switch_albedo_mip_maps(True) computes under that strategy, their
+        new colours appended to color_palette, and nodes deeper than max_depth (root = 0) are left out as
+        BoxTree.flatten_lod leaves them out. InvalidStructure for a malformed image and for one the host tree refuses
+        (a palette with duplicate entries); VhxError(VHX_E_CAPACITY) past 65,535 colours."""
+
+
 def _list_box(size, origin, extents):
     """(ox, oy, oz, gx, gy, gz) of a list / count call; extents None = the whole root cube."""
     ox, oy, oz = (int(v) for v in origin)
@@ -391,6 +418,11 @@ class TreeImage:
         translated; a half that is not selected and its palette stay. What Raytracer.compact_palettes leaves on the
         device, bit for bit; color=True, data=False is palette_compacted()."""
         return _palettes_compacted(self, color, data)
+
+    def lod(self, max_depth, method="box"):
+        return _lod(self, max_depth, method)
+
+    lod.__doc__ = _LOD_DOC
 
     def compacted(self):
         """vhx_flat_compact: this image without its unreachable node and brick slots, renumbered as the builders number
@@ -504,6 +536,11 @@ class FlatTree:
     def count_voxels(self, origin=(0, 0, 0), extents=None):
         """The number of voxels list_voxels lists for the box (a count-only call)."""
         return _list_voxels(self, origin, extents, 0)[3]
+
+    def lod(self, max_depth, method="box"):
+        return _lod(self, max_depth, method)
+
+    lod.__doc__ = _LOD_DOC
 
     @classmethod
     def _from_handle(cls, h):

@@ -1,6 +1,6 @@
 // Internal context of libvhx, shared by the translation units of the device side: vhx_device.hip (tracing), vhx_tree.hip
 // (the device tree), vhx_ctx.hip (contexts, ordering, settings), vhx_mgpu.hip, vhx_build.hip, vhx_query.hip,
-// vhx_edit.hip, vhx_points.hip, vhx_compact.hip, vhx_simplify.hip, vhx_palette.hip and vhx_list.hip.
+// vhx_edit.hip, vhx_points.hip, vhx_compact.hip, vhx_simplify.hip, vhx_palette.hip, vhx_list.hip and vhx_lod.hip.
 // Not part of the ABI: callers see vhx_ctx only as an opaque pointer (include/vhx.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -183,6 +183,14 @@ struct vhx_ctx {
     struct ListScratch {
         DevBuf fr[2], mask, first, unit, ucnt, part, ctl, out;
     } list;
+    // vhx_build_lod (vhx_lod.hip), in the destination context: per reachable node of the source its depth and the key of
+    // its place in the post-order, the colours of its MIP cells (0 = none) and whether a cell was sampled; per kept
+    // node its brick count with its first new brick and its MIP descriptor; the source of every new brick; the counters
+    // read back. Reset by each call; the node maps are the compaction's, the colour table (build.table), the table of
+    // the Solid values (build.dtable) and the scans' block sums the build's
+    struct LodScratch {
+        DevBuf depth, pkey, mcol, has, binfo, bfirst, bsrc, mips, ctl;
+    } lod;
     // depth-prepass mode (vhx_set_depth_prepass; opt-in, not the reference path)
     bool prepass = false, in_prepass = false;
     // fused hard shadows (vhx_set_shadow_light): each hit's shadow ray traced in the lane that finished its primary ray

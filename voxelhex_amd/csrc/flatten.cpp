@@ -1195,30 +1195,61 @@ int vhx_flat_list_voxels(const vhx_tree_desc *tree, const vhx_points_out *q) {
     if (!tree || !q || !q->count) return VHX_E_INVALID_ARG;
     return list_image(*tree, *q);
 }
+}  // extern "C"
+
+// the host BoxTree of the compacted image of `tree` (vhx_flat_simplify, vhx_flat_lod)
+static int host_tree_of_image(const vhx_tree_desc &tree, std::unique_ptr<BoxTree> &t) {
+    vhx_flat *packed = nullptr;
+    int rc = compact_image(tree, &packed);
+    if (rc != VHX_OK) return rc;
+    std::unique_ptr<vhx_flat> owned(packed);
+    // tree_of_flat reads solid_values by the entries' indices
+    for (size_t i = 0; i < packed->node_type.size(); ++i) {
+        const uint32_t ty = packed->node_type[i];
+        const uint32_t entries = ty == VHX_NODE_LEAF ? 64u : ty == VHX_NODE_UNIFORM_LEAF ? 1u : 0u;
+        for (uint32_t s = 0; s < entries; ++s) {
+            const uint32_t e = packed->node_children[i * 64 + s];
+            if (e != VHX_EMPTY && (e & VHX_SOLID_BIT) && (e & ~VHX_SOLID_BIT) >= packed->solid_values.size())
+                return VHX_E_TREE_INVALID_STRUCTURE;
+        }
+    }
+    t.reset(tree_of_flat(*packed));
+    return t ? VHX_OK : VHX_E_TREE_INVALID_STRUCTURE;
+}
+
+extern "C" {
+
 int vhx_flat_simplify(const vhx_tree_desc *tree, vhx_flat **out) {
     if (!out) return VHX_E_INVALID_ARG;
     *out = nullptr;
     if (!tree) return VHX_E_INVALID_ARG;
     try {
-        vhx_flat *packed = nullptr;
-        int rc = compact_image(*tree, &packed);
+        std::unique_ptr<BoxTree> t;
+        const int rc = host_tree_of_image(*tree, t);
         if (rc != VHX_OK) return rc;
-        std::unique_ptr<vhx_flat> owned(packed);
-        // tree_of_flat reads solid_values by the entries' indices
-        for (size_t i = 0; i < packed->node_type.size(); ++i) {
-            const uint32_t ty = packed->node_type[i];
-            const uint32_t entries = ty == VHX_NODE_LEAF ? 64u : ty == VHX_NODE_UNIFORM_LEAF ? 1u : 0u;
-            for (uint32_t s = 0; s < entries; ++s) {
-                const uint32_t e = packed->node_children[i * 64 + s];
-                if (e != VHX_EMPTY && (e & VHX_SOLID_BIT) && (e & ~VHX_SOLID_BIT) >= packed->solid_values.size())
-                    return VHX_E_TREE_INVALID_STRUCTURE;
-            }
-        }
-        std::unique_ptr<BoxTree> t(tree_of_flat(*packed));
-        if (!t) return VHX_E_TREE_INVALID_STRUCTURE;
-        owned.reset();
         t->simplify(0, true);
         *out = flatten_tree(*t);
+        return VHX_OK;
+    } catch (const std::bad_alloc &) {
+        return VHX_E_CAPACITY;
+    }
+}
+int vhx_flat_lod(const vhx_tree_desc *tree, uint32_t max_depth, uint32_t method, vhx_flat **out) {
+    if (!out) return VHX_E_INVALID_ARG;
+    *out = nullptr;
+    if (!tree || (method != VHX_MIP_BOX_FILTER && method != VHX_MIP_POINT_FILTER)) return VHX_E_INVALID_ARG;
+    try {
+        std::unique_ptr<BoxTree> t;
+        const int rc = host_tree_of_image(*tree, t);
+        if (rc != VHX_OK) return rc;
+        // one method and a colour-similarity threshold of 0 on every level (a level is log2(node edge / brick_dim))
+        for (size_t level = 0; level <= 32; ++level) {
+            t->mip_strategy.methods[level] = MipMethodCfg{method, 0.f};
+            t->mip_strategy.color_thresholds[level] = 0.f;
+        }
+        t->switch_albedo_mip_maps(true);
+        if (t->color_palette.size() > 0xFFFFu) return VHX_E_CAPACITY;  // a palette index has 16 bits, 0xFFFF = none
+        *out = flatten_tree(*t, max_depth, true);
         return VHX_OK;
     } catch (const std::bad_alloc &) {
         return VHX_E_CAPACITY;

@@ -1,6 +1,7 @@
-// The passes that the compaction (vhx_compact.hip) and the simplification (vhx_simplify.hip) of the resident tree share:
-// the frontier walk that renumbers the reachable nodes breadth-first, the claims of the reachable Parted bricks with
-// their source map, and the gathers that move whole bricks and their bitmaps by such a map.
+// The passes that the compaction (vhx_compact.hip), the simplification (vhx_simplify.hip) and the LOD build
+// (vhx_lod.hip) of the resident tree share: the frontier walk that renumbers the reachable nodes breadth-first, the
+// claims of the reachable Parted bricks with their source map, the gathers that move whole bricks and their bitmaps by
+// such a map, and the ranking of the distinct Solid values of a new image.
 // Each unit that includes this gets its own copy of the kernels (anonymous namespace), as with buildtab.hpp.
 //
 // Nothing of the old tree is written. A node or brick is claimed by compare-and-swap from VHX_EMPTY, and a lost claim
@@ -256,10 +257,64 @@ inline int ensure_maps(vhx_ctx *c, uint64_t nn, uint64_t nb, Maps *m, CompactCtl
     return VHX_OK;
 }
 
-// the gathers of the voxels and bitmaps of `bricks` new bricks by the map bsrc, on c's stream
+// ---- the distinct Solid values of a new image, ranked by their first key (new node * 64 + sectant), in a table of the
+// colour table's shape (vhx_simplify.hip, vhx_lod.hip). Ctl is the unit's counters: `b` the table's (ncolors distinct
+// values that are not 0, overflow, ncompact), `zero_key` the first key of the value 0 -- a legal word, but the table's
+// free-slot marker; ~0 = unused -- and `zero_rank` its index.
+template <class Ctl>
+__device__ inline void solid_insert(const ColorTable tab, Ctl *ctl, uint32_t v, u64 key) {
+    if (v == 0) {
+        if (ctl->zero_key > key) atomicMin(&ctl->zero_key, key);
+    } else {
+        color_insert(tab, &ctl->b, v, key);
+    }
+}
+
+// the table's entries compacted for the ranking (any order: the ranks come from the keys)
+template <class Ctl>
+__global__ __launch_bounds__(256) void k_smp_solid_compact(ColorTable t, Ctl *ctl) {
+    const uint32_t h = blockIdx.x * 256 + threadIdx.x;
+    if (h >= TAB_SLOTS) return;
+    const uint32_t k = t.keys[h];
+    if (k == 0) return;
+    const uint32_t pos = atomicAdd(&ctl->b.ncompact, 1u);
+    if (pos >= PAL_CAP) return;
+    t.ckey[pos] = k;
+    t.cidx[pos] = t.vals[h];
+    t.cslot[pos] = h;
+}
+
+// index of a value in solid_values = how many values have a smaller key (the keys are distinct). Element n stands for
+// the value 0, which the table cannot hold. t.pal receives solid_values, the value's table slot its index.
+template <class Ctl>
+__global__ __launch_bounds__(256) void k_smp_solid_rank(ColorTable t, Ctl *ctl) {
+    __shared__ u64 tile[256];
+    const uint32_t n = min(ctl->b.ncompact, MAX_COLORS);
+    const u64 zkey = ctl->zero_key;
+    if (blockIdx.x * 256u > n) return;  // the whole block
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    const u64 mine = i < n ? t.cidx[i] : i == n ? zkey : ~0ull;
+    uint32_t rank = 0;
+    for (uint32_t j0 = 0; j0 < n; j0 += 256) {
+        tile[threadIdx.x] = j0 + threadIdx.x < n ? t.cidx[j0 + threadIdx.x] : ~0ull;
+        __syncthreads();
+        const uint32_t m = min(256u, n - j0);
+        for (uint32_t j = 0; j < m; ++j) rank += tile[j] < mine;
+        __syncthreads();
+    }
+    if (i < n) {
+        rank += zkey < mine;
+        if (rank < PAL_CAP) t.pal[rank] = t.ckey[i];
+        t.vals[t.cslot[i]] = rank;
+    } else if (i == n && zkey != ~0ull) {
+        if (rank < PAL_CAP) t.pal[rank] = 0;
+        ctl->zero_rank = rank;
+    }
+}
+
+// the gather of the voxels of `bricks` new bricks by the map bsrc, on c's stream
 template <bool HOLES>
-inline void gather_bricks(vhx_ctx *c, const void *vsrc, void *vdst, const u64 *osrc, u64 *odst, const uint32_t *bsrc,
-                          uint32_t bricks, uint64_t n3, uint32_t occ_words) {
+inline void gather_voxels(vhx_ctx *c, const void *vsrc, void *vdst, const uint32_t *bsrc, uint32_t bricks, uint64_t n3) {
     if (n3 < 4) {
         k_cmp_gather1<HOLES><<<blocks_for(bricks), 256, 0, c->stream>>>((const uint32_t *)vsrc, (uint32_t *)vdst, bsrc,
                                                                          bricks);
@@ -273,6 +328,13 @@ inline void gather_bricks(vhx_ctx *c, const void *vsrc, void *vdst, const u64 *o
                 (const uint4 *)vsrc, (uint4 *)vdst, bsrc, w0, nwords, lgw);
         }
     }
+}
+
+// the gathers of the voxels and bitmaps of `bricks` new bricks by the map bsrc, on c's stream
+template <bool HOLES>
+inline void gather_bricks(vhx_ctx *c, const void *vsrc, void *vdst, const u64 *osrc, u64 *odst, const uint32_t *bsrc,
+                          uint32_t bricks, uint64_t n3, uint32_t occ_words) {
+    gather_voxels<HOLES>(c, vsrc, vdst, bsrc, bricks, n3);
     const uint32_t lgo = lg2(occ_words);
     const uint64_t owords = (uint64_t)bricks << lgo, ochunk = 1ull << 30;
     for (uint64_t w0 = 0; w0 < owords; w0 += ochunk)

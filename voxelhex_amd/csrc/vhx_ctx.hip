@@ -242,7 +242,9 @@ void vhx_destroy(vhx_ctx *c) {
                       &c->simplify.pmask, &c->simplify.gmask, &c->simplify.bfirst, &c->simplify.ent,
                       &c->simplify.bsrc, &c->simplify.newb, &c->simplify.ctl, &c->palette.org, &c->palette.first,
                       &c->palette.map, &c->palette.ctl, &c->palette.dfirst, &c->palette.dmap, &c->list.fr[0],
-                      &c->list.fr[1], &c->list.mask, &c->list.first, &c->list.unit, &c->list.ucnt, &c->list.part, &c->list.ctl, &c->list.out})
+                      &c->list.fr[1], &c->list.mask, &c->list.first, &c->list.unit, &c->list.ucnt, &c->list.part, &c->list.ctl, &c->list.out,
+                      &c->lod.depth, &c->lod.pkey, &c->lod.mcol, &c->lod.has, &c->lod.binfo, &c->lod.bfirst,
+                      &c->lod.bsrc, &c->lod.mips, &c->lod.ctl})
         if (b->ptr) (void)hipFree(b->ptr);
     if (c->tail_stream) {
         (void)hipStreamSynchronize(c->tail_stream);

@@ -30,7 +30,8 @@
 #include <string>
 
 #include "../../include/vhx.h"
-// the palette ranking of buildtab.hpp is not used here (the Solid values have a ranking of their own)
+// the palette ranking of buildtab.hpp is not used here (the Solid values have a ranking of their own, which
+// vhx_lod.hip shares: solid_insert, k_smp_solid_compact and k_smp_solid_rank live in treepack.hpp)
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunused-function"
 #include "treepack.hpp"
@@ -65,14 +66,6 @@ struct SimpMaps {
     uint32_t *bsrc;                       // [brick_count + node_count]
     uint32_t *newb;                       // [node_count] the brick written anew for a block-uniform leaf, else VHX_EMPTY
 };
-
-__device__ inline void solid_insert(const ColorTable tab, SimplifyCtl *ctl, uint32_t v, u64 key) {
-    if (v == 0) {
-        if (ctl->zero_key > key) atomicMin(&ctl->zero_key, key);
-    } else {
-        color_insert(tab, &ctl->b, v, key);
-    }
-}
 
 constexpr uint32_t CLS_LOADS = 4;  // 16-byte loads a thread has in flight
 
@@ -256,46 +249,6 @@ __global__ __launch_bounds__(256) void k_smp_bfill(SimpMaps sm, const SimplifyCt
     if (((mask >> lane) & 1ull) == 0) return;
     const u64 j = sm.bfirst[i] + (u64)__popcll(mask & ((1ull << lane) - 1ull));
     if (j < cap) sm.bsrc[j] = sm.ent[i * 64u + lane];
-}
-
-// the table's entries compacted for the ranking (any order: the ranks come from the keys)
-__global__ __launch_bounds__(256) void k_smp_solid_compact(ColorTable t, SimplifyCtl *ctl) {
-    const uint32_t h = blockIdx.x * 256 + threadIdx.x;
-    if (h >= TAB_SLOTS) return;
-    const uint32_t k = t.keys[h];
-    if (k == 0) return;
-    const uint32_t pos = atomicAdd(&ctl->b.ncompact, 1u);
-    if (pos >= PAL_CAP) return;
-    t.ckey[pos] = k;
-    t.cidx[pos] = t.vals[h];
-    t.cslot[pos] = h;
-}
-
-// index of a value in solid_values = how many values have a smaller key (the keys are distinct). Element n stands for
-// the value 0, which the table cannot hold. t.pal receives solid_values, the value's table slot its index.
-__global__ __launch_bounds__(256) void k_smp_solid_rank(ColorTable t, SimplifyCtl *ctl) {
-    __shared__ u64 tile[256];
-    const uint32_t n = min(ctl->b.ncompact, MAX_COLORS);
-    const u64 zkey = ctl->zero_key;
-    if (blockIdx.x * 256u > n) return;  // the whole block
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    const u64 mine = i < n ? t.cidx[i] : i == n ? zkey : ~0ull;
-    uint32_t rank = 0;
-    for (uint32_t j0 = 0; j0 < n; j0 += 256) {
-        tile[threadIdx.x] = j0 + threadIdx.x < n ? t.cidx[j0 + threadIdx.x] : ~0ull;
-        __syncthreads();
-        const uint32_t m = min(256u, n - j0);
-        for (uint32_t j = 0; j < m; ++j) rank += tile[j] < mine;
-        __syncthreads();
-    }
-    if (i < n) {
-        rank += zkey < mine;
-        if (rank < PAL_CAP) t.pal[rank] = t.ckey[i];
-        t.vals[t.cslot[i]] = rank;
-    } else if (i == n && zkey != ~0ull) {
-        if (rank < PAL_CAP) t.pal[rank] = 0;
-        ctl->zero_rank = rank;
-    }
 }
 
 // one thread per (new node, sectant); runs only for a tree that passed the checks

@@ -680,4 +680,18 @@ int vhx_set_node_mips(vhx_ctx *c, const uint32_t *node_mips, uint32_t count) {
     return ws.end();
 }
 
+int vhx_read_node_mips(vhx_ctx *c, uint32_t *out, uint32_t count) {
+    if (!c || !out) return VHX_E_INVALID_ARG;
+    if (!c->tree->uploaded || !c->tree->mips_on) return fail(c, VHX_E_STATE, "vhx_read_node_mips: no node MIPs are set");
+    if (count != c->tree->desc.node_count) return fail(c, VHX_E_INVALID_ARG, "vhx_read_node_mips: count != node_count");
+    VHX_HIP(c, hipSetDevice(c->device));
+    VHX_STREAM(c);
+    TraceScope tscope(c);  // after the tree's last write
+    if (tscope.rc) return tscope.rc;
+    if (!c->tree->mips_on) return fail(c, VHX_E_STATE, "vhx_read_node_mips: no node MIPs are set");
+    VHX_HIP(c, hipMemcpyAsync(out, c->tree->mips.ptr, (uint64_t)count * 4, hipMemcpyDeviceToHost, c->stream));
+    VHX_HIP(c, hipStreamSynchronize(c->stream));
+    return tscope.end();
+}
+
 }  // extern "C"

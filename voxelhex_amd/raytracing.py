@@ -726,6 +726,33 @@ class Raytracer:
         self._mips = np.ascontiguousarray(node_mips, np.uint32)
         self._check(N.lib().vhx_set_node_mips(self._h, self._mips.ctypes.data, len(self._mips)))
 
+    def node_mips(self):
+        """vhx_read_node_mips: the node MIP descriptors in force (set_node_mips, build_lod), one per node, as a uint32
+        array read back from the device. VHX_E_STATE when none are set."""
+        a = np.empty(self.tree_counts().node_count, np.uint32)
+        self._check(N.lib().vhx_read_node_mips(self._h, a.ctypes.data, a.size))
+        return a
+
+    def build_lod(self, source, max_depth, method="box"):
+        """vhx_build_lod: makes this context's tree the LOD image of `source`'s resident tree with node MIPs, computed
+        on the device without leaving it (download() and node_mips() then equal source.download().lod(max_depth,
+        method), bit for bit). Every node's albedo MIP brick is resampled bottom-up with `method` ("box": BoxFilter,
+        "point": PointFilter) on every level and colour-similarity thresholds of 0, nodes deeper than max_depth (root =
+        0) are left out, and the descriptors are set as set_node_mips sets them, so a trace of this context shows a
+        parent's MIP where a child was cut. `source` is only read: it stays MIP-free and editable, and the call is made
+        again after edits. Returns (nodes, bricks, colors_added). Owner context only; frames in flight on this context's
+        tree finish with the old tree. A refused call leaves both contexts as they were: VHX_E_STATE for a source without
+        a tree, with node MIPs, or not of canonical depth, and for a shadow light on this context; VHX_E_INVALID_ARG for
+        the same tree on both sides or different devices; VHX_E_CAPACITY past 65,535 colours (BoxFilter appends the
+        colours it creates; PointFilter creates none). DESIGN.md §8.16."""
+        from .boxtree import mip_method_code
+        n, b, k = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        self._check(N.lib().vhx_build_lod(self._h, source._h, int(max_depth), mip_method_code(method), ctypes.byref(n),
+                                          ctypes.byref(b), ctypes.byref(k)))
+        self._tree = _BuiltOnDevice()
+        self._mips = None  # the descriptors live on the device (node_mips() reads them)
+        return n.value, b.value, k.value
+
     def set_depth_prepass(self, enable=True, margin=0.0):
         """vhx_set_depth_prepass: the opt-in half-resolution depth-prepass fast mode (not the reference's semantics)."""
         self._check(N.lib().vhx_set_depth_prepass(self._h, 1 if enable else 0, float(margin)))
