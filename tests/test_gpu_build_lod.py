@@ -1,6 +1,9 @@
 """vhx_build_lod (Raytracer.build_lod): the LOD image of a device tree with node MIPs, built on the GPU. The device
 result is compared bit for bit with vhx_flat_lod (FlatTree.lod / TreeImage.lod) of the source's download, which
-tests/test_lod_model.py pins to the host BoxTree route; frames are compared with a context that uploaded the host image."""
+tests/test_lod_model.py pins to the host BoxTree route. The frames here are compared between two GPU contexts, the
+built one and one that uploaded the host image with its descriptors: both run the same MIP kernels, so these frames pin
+the image and the descriptors, not the kernels. The oracle's trace of the downloaded image against the device's is in
+tests/test_gpu_mip_parity.py (test_device_built_lod_vs_oracle)."""
 import ctypes
 
 import numpy as np
@@ -11,7 +14,7 @@ from voxelhex_amd import _native as N
 from voxelhex_amd.boxtree import BoxTree
 from tests import _dense_grids as G
 from tests import _lod_grids as L
-from tests import _points_model as PM
+from tests._mip_cases import build_lod_source
 from tests._skycams import aimed_camera
 
 pytestmark = pytest.mark.gpu
@@ -35,35 +38,13 @@ def _cams(size):
             aimed_camera(W, H, (0.2 * size, 0.3 * size, -0.6 * size), (0.1 * size, 0.1 * size, 0.2 * size), fov=2.0)]
 
 
-def _build_src(src, name, kind):
-    size, bd, _ = L.SHAPES[name]
-    g, d = L.pair(name)
-    src.build_dense(g, size, bd, data=d, simplify=kind == "simplified")
-    if kind != "edited":
-        return
-    # scattered inserts, clears and a dense box, without compaction: orphaned slots and edit-order numbering
-    rng = np.random.default_rng(size * 7 + bd)
-    q = max(size // 4, 2)
-    pos, a, dd = PM.random_points(rng, size, 40 * q, G.COLORS, [0, 5, 9], hi=(q + 5 if size > 4 else 4,) * 3)
-    src.set_voxels(pos, a, dd, "insert")
-    src.clear_voxels(pos[::3])
-    box = np.where(rng.random((q // 2 + 1, 3, q)) < 0.5, G.COLORS[1], 0).astype(np.uint32)
-    src.write_dense(box, origin=(1, 0, 1) if size > 4 else (0, 0, 0))
-    if size > 4:  # the first leaf cleared as a whole, which unlinks it, and a voxel put back: a new leaf at the end
-        src.fill_box((0, 0, 0), (4 * bd,) * 3, 0)
-        src.set_voxels(np.array([[1, 1, 1]], np.uint32), G.COLORS[0], 0, "insert")
-    src.set_voxels(pos[1::5], G.COLORS[4], 11, "replace")
-    if size > 4:
-        assert src.orphans() != (0, 0), "the edits left no orphaned slot"
-
-
 @pytest.mark.parametrize("method", L.METHODS)
 @pytest.mark.parametrize("kind", ["plain", "simplified", "edited"])
 @pytest.mark.parametrize("name", list(L.SHAPES))
 def test_build_lod_is_the_host_image(ctxs, name, kind, method):
     src, lod, _ = ctxs
     depth = L.SHAPES[name][2]
-    _build_src(src, name, kind)
+    build_lod_source(src, name, kind)
     before = src.download()
     if kind == "edited" and name != "4/1":  # edit order: not the numbering a compaction gives
         assert not np.array_equal(before.node_children, before.compacted().node_children), "the edits renumbered nothing"
@@ -89,7 +70,7 @@ def test_build_lod_is_the_host_image(ctxs, name, kind, method):
 def test_lod_frames_equal_an_uploaded_host_lod(ctxs, name, method):
     src, lod, ref = ctxs
     size, bd, depth = L.SHAPES[name]
-    _build_src(src, name, "plain")
+    build_lod_source(src, name, "plain")
     host = src.download()
     cams = _cams(size)
     exact = [src.trace_primary(c, fields=FIELDS) for c in cams]
@@ -120,7 +101,7 @@ def test_build_lod_again_after_an_edit_is_ordered_like_an_upload(ctxs):
     src, _, ref = ctxs
     name, d, method, F = "64/4", 0, "box", 4
     size = L.SHAPES[name][0]
-    _build_src(src, name, "plain")
+    build_lod_source(src, name, "plain")
     cams = [aimed_camera(W, H, (-0.8 * size, (1.0 + 0.1 * i) * size, -1.1 * size), (size / 2, size / 4, size / 2))
             for i in range(F)]
     owner = vhx.Raytracer(0)
@@ -178,7 +159,7 @@ def _refused(dst, src_h, code, d=1, method=N.VHX_MIP_BOX_FILTER, dst_h=None, out
 def test_build_lod_refusals(ctxs):
     src, lod, other = ctxs
     size, bd, depth = L.SHAPES["64/4"]
-    _build_src(src, "64/4", "plain")
+    build_lod_source(src, "64/4", "plain")
     before = src.download()
     lod.build_lod(src, 1, "box")
     # arguments
