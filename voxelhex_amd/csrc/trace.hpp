@@ -299,6 +299,83 @@ __device__ __forceinline__ void fill_hit(HitOut &h, uint32_t v, uint32_t cell, F
     h.vz = ras_u32(hb.min.z);
 }
 
+// The float half of one walk trip (dda_step_to_next_sibling, cpu.rs:104-132, in exit-plane form): the distance to the
+// nearest exit plane and the axes that reach it. It reads registers only.
+// (m and the three flags are separate variables in the caller: a struct of them is carried round the loop as one packed
+// word that every trip takes apart again)
+__device__ __forceinline__ void trip_select(F2 exy, float ez, F2 pxy, float pz, F2 sfxy, float sfz, float &m, bool &mx,
+                                            bool &my, bool &mz) {
+    const F2 sxy = (exy - pxy) * sfxy;
+    const float dx = __builtin_fabsf(sxy.x), dy = __builtin_fabsf(sxy.y), dz = __builtin_fabsf((ez - pz) * sfz);
+    m = __builtin_fminf(__builtin_fminf(dx, dy), dz);
+    mx = m == dx;
+    my = m == dy;
+    mz = m == dz;
+}
+
+// The cell walk of both DDA loops: the brick-cell walk of probe_brick (G = brick_dim) and the ADVANCE / POP walk over a
+// node's sectants (G = 4, ADV). It steps from an empty cell and tests the one stepped into, so every trip commits its
+// step and the loop has one exit: the walk left the grid | the cell is occupied | the iteration bound.
+//   pxy, pz    the ray point, advanced trip by trip;
+//   exy, ez    the exit planes of the current cell, e_k = cmin_k + unit * max(sg_k, 0), moved by sgu_k = sg_k * unit on
+//              the axes that step;
+//   jf         the direction-normalised flat cell index jx + G * jy + G^2 * jz (j_k = i_k, or G-1-i_k for a negative
+//              direction, so a step adds 1); the cell's flat index is jf ^ F;
+//   word       the occupancy word of cell jf ^ F (WORDS > 1: reloaded from occw when the walk crosses into another);
+//   oob        on return, non-zero iff the walk left the grid (jf is meaningless then).
+// The loop is written with the float half of a trip (trip_select) ahead of it and at its bottom, behind the exit test:
+// a trip commits its step, tests the cell it stepped into, and only the lanes that go on compute the next trip's
+// distances. Every float operation and its operands are those of the reference's order, so the values are the same
+// bit for bit. A wave on its own takes 17 % longer per step in this form than in the loops it stands beside, and the
+// full SIMDs of a batch's pass 0 run it faster: only k_trace_primary_batch walks this way (FLAT).
+// The integer half carries one register: jf advances by the three selected strides in one add, independent of each
+// other. An axis leaves the grid exactly when its field of jf carries out, and jf ^ old jf ^ increment is the word of
+// carries into each bit, so the bits G, G^2 and G^3 of it are the out-of-bounds test (a carry that ripples on from a
+// lower field sets a higher one of them too: the walk has left the grid either way). G = 1 has no fields: every step
+// leaves.
+// iters counts trips; the bound test is the caller's form (ADV: the POP / ADVANCE loop tests iters - 1).
+template <int G, uint32_t WORDS, bool COUNT, bool ADV>
+__device__ __forceinline__ void walk_cells(F2 &pxy, float &pz, F2 &exy, float &ez, const F2 sguxy, const float sguz,
+                                           const F2 dxy, const float dz, const F2 sfxy, const float sfz, uint32_t &jf,
+                                           const uint32_t F, uint64_t &word, const uint64_t *occw, const uint32_t *vox,
+                                           uint32_t &oob, uint32_t &iters, uint32_t &bytes, uint32_t pp) {
+    static_assert(VHX_MAX_ITERS == (1u << 22), "bound test below");
+    (void)pp;
+    int32_t word_idx = (int32_t)((jf ^ F) >> 6);
+    float m;
+    bool mx, my, mz;
+    trip_select(exy, ez, pxy, pz, sfxy, sfz, m, mx, my, mz);
+    for (;;) {
+        VHX_PROF_BLOCK(pp, ADV ? 6 : 2);
+        ++iters;
+        // commit the trip
+        pxy = pxy + dxy * m;
+        pz = pz + dz * m;
+        const F2 en = exy + sguxy;
+        exy = mk2(mx ? en.x : exy.x, my ? en.y : exy.y);
+        ez = mz ? ez + sguz : ez;
+        const uint32_t inc = (mx ? 1u : 0u) | (my ? (uint32_t)G : 0u) | (mz ? (uint32_t)(G * G) : 0u);
+        const uint32_t jn = jf + inc;
+        oob = G == 1 ? jn : (jn ^ jf ^ inc) & (uint32_t)(G | (G * G) | (G * G * G));
+        jf = jn;
+        // the exit test is one integer word (left the grid | occupied | bound)
+        const uint32_t uflat = jf ^ F;
+        if (WORDS > 1) {
+            const int32_t wi = (int32_t)(uflat >> 6);
+            if (oob == 0u && wi != word_idx) {
+                word_idx = wi;
+                word = occw[wi];
+            }
+        }
+        const uint32_t bit = (uint32_t)(word >> (uflat & 63u)) & 1u;  // meaningless once oob (exit anyway)
+        if (COUNT && oob == 0u) bytes += 4 + pal_bytes<COUNT>(vox[uflat]);  // the reference reads every cell's palettes
+        // the bound only ends a ray whose steps make no progress (a zero or NaN direction); at the bound the oracle
+        // tests the cell it stepped into and stops before the next step, like this exit
+        if ((oob | bit | ((iters - (ADV ? 1u : 0u)) >> 22)) != 0u) break;
+        trip_select(exy, ez, pxy, pz, sfxy, sfz, m, mx, my, mz);
+    }
+}
+
 // probe_brick (cpu.rs:236-292) incl. traverse_brick (cpu.rs:136-232).
 // The entry cell is tested before the loop; the loop steps from an empty cell and tests the next one, so every
 // iteration commits its step unconditionally and the loop has a single exit (left the brick, or hit). A brick walk
@@ -306,7 +383,8 @@ __device__ __forceinline__ void fill_hit(HitOut &h, uint32_t v, uint32_t cell, F
 // walk only the VHX_MAX_ITERS bound is checked (the DDA arithmetic is described at the loop). Returns true on a hit,
 // with the hit cell's flat index in `hflat` (-1 for a Solid brick); the hit record itself is filled after the
 // traversal loop (finish_hit), so the loop carries two registers for it instead of a dozen.
-template <bool COUNT, int BD>
+// FLAT: the cell walk through walk_cells (the batch pass 0) instead of the loop written out here.
+template <bool COUNT, int BD, bool FLAT = false>
 __device__ __forceinline__ bool probe_brick(const DevTree &t, const RayD &r, F3d &p, uint32_t desc, uint64_t cocc,
                                             CubeD bb, HitOut &h, uint32_t &iters, int32_t &hflat, uint32_t pp = 0) {
     // one branch (a Parted brick's walk); Empty and Solid (cpu.rs:249-260) resolve by selects. VHX_EMPTY has the
@@ -355,49 +433,61 @@ __device__ __forceinline__ bool probe_brick(const DevTree &t, const RayD &r, F3d
             const uint32_t fx = spos(r.sg.x) ? 0u : BD - 1u, fy = spos(r.sg.y) ? 0u : BD - 1u,
                            fz = spos(r.sg.z) ? 0u : BD - 1u;
             const uint32_t F = fx + fy * BD + fz * (BD * BD);
-            uint32_t jx = (uint32_t)ix ^ fx, jy = (uint32_t)iy ^ fy, jz = (uint32_t)iz ^ fz;
-            for (;;) {
-                VHX_PROF_BLOCK(pp, 2);
-                ++iters;
-                // dda_step_to_next_sibling (cpu.rs:104-132) on the cell {cmin, unit}
-                const F2 sxy = (exy - pxy) * sfxy;
-                const float dx = __builtin_fabsf(sxy.x), dy = __builtin_fabsf(sxy.y),
-                            dz = __builtin_fabsf((ez - pz) * r.sfz);
-                const float m = __builtin_fminf(__builtin_fminf(dx, dy), dz);
-                pxy = pxy + dxy * m;
-                pz = pz + r.dz * m;
-                const bool mx = m == dx, my = m == dy, mz = m == dz;
-                const F2 en = exy + sguxy;
-                exy = mk2(mx ? en.x : exy.x, my ? en.y : exy.y);
-                ez = mz ? ez + sguz : ez;
-                jx += (uint32_t)mx;
-                jy += (uint32_t)my;
-                jz += (uint32_t)mz;
-                // the exit test is one integer word (left the brick | occupied cell | iteration bound), so the loop's
-                // control costs one compare instead of a chain of mask operations
-                const uint32_t oob = (jx | jy | jz) & ~(uint32_t)(BD - 1);  // non-zero iff the walk left the brick
-                const uint32_t uflat = (jx + jy * BD + jz * (BD * BD)) ^ F;
-                if (B::WORDS > 1) {
-                    const int32_t wi = (int32_t)(uflat >> 6);
-                    if (oob == 0u && wi != word_idx) {
-                        word_idx = wi;
-                        word = occw[wi];
+            if constexpr (FLAT) {
+                uint32_t jf = (uint32_t)flat ^ F, oob;
+                uint32_t bytes = 0;
+                walk_cells<BD, B::WORDS, COUNT, false>(pxy, pz, exy, ez, sguxy, sguz, dxy, r.dz, sfxy, r.sfz, jf, F,
+                                                       word, occw, vox, oob, iters, bytes, pp);
+                if (COUNT) h.bytes += bytes;
+                p = mk(pxy.x, pxy.y, pz);
+                asm volatile("" : "+v"(jf), "+v"(oob));
+                flat = (int32_t)(jf ^ F);
+                hit = oob == 0u && ((word >> (flat & 63)) & 1ull) != 0ull;
+            } else {
+                uint32_t jx = (uint32_t)ix ^ fx, jy = (uint32_t)iy ^ fy, jz = (uint32_t)iz ^ fz;
+                for (;;) {
+                    VHX_PROF_BLOCK(pp, 2);
+                    ++iters;
+                    // dda_step_to_next_sibling (cpu.rs:104-132) on the cell {cmin, unit}
+                    const F2 sxy = (exy - pxy) * sfxy;
+                    const float dx = __builtin_fabsf(sxy.x), dy = __builtin_fabsf(sxy.y),
+                                dz = __builtin_fabsf((ez - pz) * r.sfz);
+                    const float m = __builtin_fminf(__builtin_fminf(dx, dy), dz);
+                    pxy = pxy + dxy * m;
+                    pz = pz + r.dz * m;
+                    const bool mx = m == dx, my = m == dy, mz = m == dz;
+                    const F2 en = exy + sguxy;
+                    exy = mk2(mx ? en.x : exy.x, my ? en.y : exy.y);
+                    ez = mz ? ez + sguz : ez;
+                    jx += (uint32_t)mx;
+                    jy += (uint32_t)my;
+                    jz += (uint32_t)mz;
+                    // the exit test is one integer word (left the brick | occupied cell | iteration bound), so the
+                    // loop's control costs one compare instead of a chain of mask operations
+                    const uint32_t oob = (jx | jy | jz) & ~(uint32_t)(BD - 1);  // non-zero iff the walk left the brick
+                    const uint32_t uflat = (jx + jy * BD + jz * (BD * BD)) ^ F;
+                    if (B::WORDS > 1) {
+                        const int32_t wi = (int32_t)(uflat >> 6);
+                        if (oob == 0u && wi != word_idx) {
+                            word_idx = wi;
+                            word = occw[wi];
+                        }
                     }
+                    const uint32_t bit = (uint32_t)(word >> (uflat & 63u)) & 1u;  // meaningless once oob (exit anyway)
+                    if (COUNT && oob == 0u) h.bytes += 4 + pal_bytes<COUNT>(vox[uflat]);
+                    // the bound only ends a ray whose steps make no progress (a zero or NaN direction); at the bound
+                    // the oracle tests the cell it stepped into and stops before the next step, like this exit
+                    static_assert(VHX_MAX_ITERS == (1u << 22), "bound test below");
+                    if ((oob | bit | (iters >> 22)) != 0u) break;
                 }
-                const uint32_t bit = (uint32_t)(word >> (uflat & 63u)) & 1u;  // meaningless once oob (exit anyway)
-                if (COUNT && oob == 0u) h.bytes += 4 + pal_bytes<COUNT>(vox[uflat]);
-                // the bound only ends a ray whose steps make no progress (a zero or NaN direction); at the bound the
-                // oracle tests the cell it stepped into and stops before the next step, like this exit
-                static_assert(VHX_MAX_ITERS == (1u << 22), "bound test below");
-                if ((oob | bit | (iters >> 22)) != 0u) break;
+                // hit = the exit test, recomputed once from the final cell instead of carrying the loop's booleans out
+                // of it (opaque copies keep the compiler from reusing the in-loop values, which costs mask bookkeeping
+                // per cell)
+                p = mk(pxy.x, pxy.y, pz);
+                asm volatile("" : "+v"(jx), "+v"(jy), "+v"(jz));
+                flat = (int32_t)((jx + jy * BD + jz * (BD * BD)) ^ F);
+                hit = (jx | jy | jz) < (uint32_t)BD && ((word >> (flat & 63)) & 1ull) != 0ull;
             }
-            // hit = the exit test, recomputed once from the final cell instead of carrying the loop's booleans out of
-            // it (opaque copies keep the compiler from reusing the in-loop values, which costs mask bookkeeping per
-            // cell)
-            p = mk(pxy.x, pxy.y, pz);
-            asm volatile("" : "+v"(jx), "+v"(jy), "+v"(jz));
-            flat = (int32_t)((jx + jy * BD + jz * (BD * BD)) ^ F);
-            hit = (jx | jy | jz) < (uint32_t)BD && ((word >> (flat & 63)) & 1ull) != 0ull;
         }
     }
     hflat = flat;
@@ -479,7 +569,7 @@ __device__ __forceinline__ void save_state(uint4 *st, F3d p, uint32_t iters, Cub
 // every way out of it sets the exit code `ex` and leaves through a single exit at the bottom of the iteration. The
 // NodeStack<u32, 4> ring (cpu.rs:18-76) is a shift register: `node` is its top, s1..s3 the entries below; a push onto
 // a full stack drops the oldest entry, a pop that empties it ends the walk and restarts from the root.
-template <bool COUNT, int BD, bool MIP = false>
+template <bool COUNT, int BD, bool MIP = false, bool FLAT = false>
 struct Trav {
     RayD r;
     uint32_t dir_idx;
@@ -615,7 +705,7 @@ struct Trav {
             hdesc = Brick<BD>::WORDS == 1 || !uniform ? slot : t.children[(uint64_t)node * 64u];
             CubeD bb = uniform ? cur : tb;
             if (!uniform && tbok == 0u) bb = child_bounds(cur, target);
-            ex = probe_brick<COUNT, BD>(t, r, p, hdesc, cocc, bb, h, iters, hflat, pp) ? 1u : 0u;
+            ex = probe_brick<COUNT, BD, FLAT>(t, r, p, hdesc, cocc, bb, h, iters, hflat, pp) ? 1u : 0u;
 #if VHX_CHAIN
             h.chain.nprobe += 1;
 #endif
@@ -642,7 +732,7 @@ struct Trav {
                         Brick<BD>::WORDS == 1 && (mdesc & VHX_SOLID_BIT) == 0u ? t.brick_occ[mdesc] : 0ull;
                     F3d pm = p;
                     int32_t mflat;
-                    if (probe_brick<COUNT, BD>(t, r, pm, mdesc, mocc, cur, h, iters, mflat)) {
+                    if (probe_brick<COUNT, BD, FLAT>(t, r, pm, mdesc, mocc, cur, h, iters, mflat)) {
                         p = pm;
                         hdesc = mdesc;
                         hflat = mflat;
@@ -721,36 +811,49 @@ struct Trav {
                 const F3d sgs = mk(r.sg.x * tb.size, r.sg.y * tb.size, r.sg.z * tb.size);
                 const uint32_t fx = spos(r.sg.x) ? 0u : 3u, fy = spos(r.sg.y) ? 0u : 3u, fz = spos(r.sg.z) ? 0u : 3u;
                 const uint32_t F = fx + fy * 4u + fz * 16u;
+                // (FLAT: the three counters are unused, the walk carries their flat index)
                 uint32_t jx = (target & 3u) ^ fx, jy = ((target >> 2) & 3u) ^ fy, jz = (target >> 4) ^ fz;
                 F2 exy = mk2(tb.min.x + usg.x, tb.min.y + usg.y);
                 float ez = tb.min.z + usg.z;
                 const F2 sgsxy = mk2(sgs.x, sgs.y), sfxy = r.sfxy, dxy = r.dxy;
                 F2 pxy = mk2(p.x, p.y);
                 float pz = p.z;
-                for (;;) {
-                    VHX_PROF_BLOCK(pp, 6);
-                    ++iters;
-                    const F2 sxy = (exy - pxy) * sfxy;
-                    const float dx = __builtin_fabsf(sxy.x), dy = __builtin_fabsf(sxy.y),
-                                dz = __builtin_fabsf((ez - pz) * r.sfz);
-                    const float m = __builtin_fminf(__builtin_fminf(dx, dy), dz);
-                    pxy = pxy + dxy * m;
-                    pz = pz + r.dz * m;
-                    const bool mx = m == dx, my = m == dy, mz = m == dz;
-                    const F2 en = exy + sgsxy;
-                    exy = mk2(mx ? en.x : exy.x, my ? en.y : exy.y);
-                    ez = mz ? ez + sgs.z : ez;
-                    jx += (uint32_t)mx;
-                    jy += (uint32_t)my;
-                    jz += (uint32_t)mz;
-                    const uint32_t oob = (jx | jy | jz) & ~3u;  // non-zero iff the walk left the node
-                    const uint32_t tg = (jx + jy * 4u + jz * 16u) ^ F;
-                    const uint32_t bit = (uint32_t)(wocc >> (tg & 63u)) & 1u;
-                    if ((oob | bit | ((iters - 1u) >> 22)) != 0u) break;  // left | occupied | iters > 2^22
+                if constexpr (FLAT) {
+                    uint32_t jf = target ^ F, oob;  // target < 64 here (a larger one popped)
+                    uint64_t word = wocc;
+                    uint32_t nobytes = 0;
+                    // the exit: left the node | occupied sectant | iters > 2^22
+                    walk_cells<4, 1u, false, true>(pxy, pz, exy, ez, sgsxy, sgs.z, dxy, r.dz, sfxy, r.sfz, jf, F, word,
+                                                   nullptr, nullptr, oob, iters, nobytes, pp);
+                    p = mk(pxy.x, pxy.y, pz);
+                    asm volatile("" : "+v"(jf), "+v"(oob));
+                    target = oob == 0u ? jf ^ F : 64u;
+                } else {
+                    for (;;) {
+                        VHX_PROF_BLOCK(pp, 6);
+                        ++iters;
+                        const F2 sxy = (exy - pxy) * sfxy;
+                        const float dx = __builtin_fabsf(sxy.x), dy = __builtin_fabsf(sxy.y),
+                                    dz = __builtin_fabsf((ez - pz) * r.sfz);
+                        const float m = __builtin_fminf(__builtin_fminf(dx, dy), dz);
+                        pxy = pxy + dxy * m;
+                        pz = pz + r.dz * m;
+                        const bool mx = m == dx, my = m == dy, mz = m == dz;
+                        const F2 en = exy + sgsxy;
+                        exy = mk2(mx ? en.x : exy.x, my ? en.y : exy.y);
+                        ez = mz ? ez + sgs.z : ez;
+                        jx += (uint32_t)mx;
+                        jy += (uint32_t)my;
+                        jz += (uint32_t)mz;
+                        const uint32_t oob = (jx | jy | jz) & ~3u;  // non-zero iff the walk left the node
+                        const uint32_t tg = (jx + jy * 4u + jz * 16u) ^ F;
+                        const uint32_t bit = (uint32_t)(wocc >> (tg & 63u)) & 1u;
+                        if ((oob | bit | ((iters - 1u) >> 22)) != 0u) break;  // left | occupied | iters > 2^22
+                    }
+                    p = mk(pxy.x, pxy.y, pz);
+                    asm volatile("" : "+v"(jx), "+v"(jy), "+v"(jz));
+                    target = (jx | jy | jz) < 4u ? (jx + jy * 4u + jz * 16u) ^ F : 64u;
                 }
-                p = mk(pxy.x, pxy.y, pz);
-                asm volatile("" : "+v"(jx), "+v"(jy), "+v"(jz));
-                target = (jx | jy | jz) < 4u ? (jx + jy * 4u + jz * 16u) ^ F : 64u;
                 tb.min = mk(exy.x - usg.x, exy.y - usg.y, ez - usg.z);  // exact: undoes the exact e = tb.min + usg
                 if (pop) {
                     iters -= 1u;  // POP's step is not one of the walk's steps
@@ -812,12 +915,12 @@ struct Trav {
 // the wave's issue slots for a few lanes. 0 = off. The result is the same either way (the traversal is deterministic).
 // rbase (queue-state mode): a resumed ray's state is read at rbase + 4 * ridx and an abandoned ray's is saved at
 // sbase + 4 * (sidx + its rank among the wave's abandoned rays) (Trav::end); without it both use sbase + 4 * sidx.
-template <bool COUNT, int BD, bool START = false, bool MIP = false>
+template <bool COUNT, int BD, bool START = false, bool MIP = false, bool FLAT = false>
 __device__ __forceinline__ bool get_by_ray(const DevTree &t, const uint64_t *occ_tab, F3d o, F3d d, HitOut &h,
                                            uint32_t budget, uint4 *sbase = nullptr, uint32_t sidx = 0,
                                            bool resume = false, float start = 0.0f, uint32_t sparse = 0,
                                            const uint4 *rbase = nullptr, uint32_t ridx = 0, bool slots = false) {
-    Trav<COUNT, BD, MIP> tr;
+    Trav<COUNT, BD, MIP, FLAT> tr;
     VHX_PROF_BLOCK(pass_of_budget(budget), 10);
     h.iters = 0;
     if (!tr.template begin<START>(t, o, d, h, rbase ? rbase : sbase, rbase ? ridx : sidx, resume, start)) return true;

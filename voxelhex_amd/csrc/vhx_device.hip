@@ -1171,7 +1171,8 @@ __global__ void __launch_bounds__(256) VHX_BATCH_ATTR k_trace_primary_batch(DevT
             h.iters = 0;
         } else {
             primary_ray(cam, px, py, o, d);
-            done = get_by_ray<false, BD>(t, occ_tab, o, d, h, q.budget, q.state,
+            // FLAT: the walks in the form that full SIMDs run fastest (trace.hpp, walk_cells)
+            done = get_by_ray<false, BD, false, false, true>(t, occ_tab, o, d, h, q.budget, q.state,
                                          q.qmode ? (pos * 4u + wave) * 64u : (uint32_t)idx, false, 0.0f, q.sparse,
                                          nullptr, 0, q.qmode != 0);
         }
